@@ -27,6 +27,11 @@ Multi-GPU (torchrun): vertices split into 64-aligned blocks; rank r owns rows
 of the next frontier with GrB_mxv (q_r<!v_r.S,replace> = A^T_r lor.land q);
 the frontier bitmap (n/8 bytes) is all-gathered over RCCL each level -- the
 path's only exchange step.  Total work is fixed (strong scaling).
+
+A plain run sets up (ingest, the timed roots' edge counts), warms up, times --steps BFS,
+writes the last one's levels with --dump-outputs DIR and prints the headline line.  --full
+adds everything else described above and below: the parity checks against the oracle, the
+roofline pass, cpu_baseline and the `secondary` lines (the --no-* options trim a --full run).
 """
 import argparse
 import ctypes
@@ -71,6 +76,13 @@ def parse():
     p.add_argument("--scale", type=int, default=22)
     p.add_argument("--edge-factor", type=int, default=16)
     p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline line's timed steps also run what a plain run leaves out: the parity "
+                        "checks against the oracle, the roofline pass, the stream-copy ceiling, the secondary "
+                        "workloads (other semiring, multi-source BFS, configs 2 / 4 / 5) and the CPU baselines")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (the BFS level of every vertex, 0 = not "
+                        "reached) to DIR/levels.npy (float32; DIR/levels_rank<r>.npy per rank at N > 1)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-secondary", action="store_true", help="skip the config 2 / config 4 lines")
     p.add_argument("--no-msbfs", action="store_true", help="skip the multi-source (masked mxm) BFS line")
@@ -133,6 +145,23 @@ def vector_indices(lib, v):
     ok(lib.GrB_Vector_extractTuples_INT32(ctypes.c_void_p(idx.ctypes.data), ctypes.c_void_p(lv.ctypes.data),
                                           ctypes.byref(nv), v), "extract")
     return idx.astype(np.int64), lv
+
+
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs: all files of one run together
+
+
+def dump_levels(dirpath, name, idx, lv, nloc, seed, budget=DUMP_MAX_BYTES):
+    """--dump-outputs: the level vector a caller of the timed loop receives (GrB_Vector v, INT32,
+    entries = reached vertices) as a dense float32 array, 0 = no entry.  A vector too long for the
+    budget is written as a fixed sample: the positions drawn by default_rng(seed), ascending."""
+    dense = np.zeros(nloc, np.float32)
+    dense[idx] = lv
+    keep = budget // 4
+    if nloc > keep:
+        dense = dense[np.sort(np.random.default_rng(seed).choice(nloc, keep, replace=False))]
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, name + ".npy"), dense)
+
 
 def _time_calls(torch, stream, fn, reps):
     """GPU time per call of fn (HIP events on the library stream, GPU kept busy ahead)."""
@@ -831,6 +860,8 @@ def config5_spgemm(lib, torch, stream, O, dist, world, rank, args, sc, cpu=False
 
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1075,13 +1106,16 @@ def main():
             e = int(t.item())
         return e, idx, lv
 
-    # verification (untimed): GPU levels == oracle levels for root 0; edge counts per root
+    # untimed: edge counts per root (a plain run: of the roots its timed steps use); --full:
+    # GPU levels == oracle levels for root 0
     edges = []
     parity = None
-    for k, src in enumerate(roots):
+    for k, src in enumerate(roots if args.full else roots[:args.steps]):
         bfs(src, False)
         e, idx, lv = reached_edges()
         edges.append(e)
+        if not args.full:
+            continue
         if k == 0 and world == 1:
             G = O.Csr(n, n, "BOOL", ap, ai, np.ones(ai.size, np.bool_))
             lev_ref, _, _ = O.bfs_levels(G, int(src))
@@ -1132,6 +1166,52 @@ def main():
     gteps = total_edges / elapsed / 1e9
     # Graph500 convention: harmonic mean of the per-root TEPS (rank 0's clock)
     hm = len(per_bfs) / sum(t / edges[s % len(roots)] for s, t in enumerate(per_bfs)) / 1e9
+
+    if args.dump_outputs:
+        # v as the last timed BFS left it (nothing has run since)
+        idx, lv = vector_indices(lib, v)
+        dump_levels(args.dump_outputs, "levels" if world == 1 else f"levels_rank{rank}", idx, lv, nloc,
+                    args.seed, DUMP_MAX_BYTES // world)
+
+    out = {
+        "metric": "GTEPS (masked mxv/vxm level-BFS, R-MAT s22)",
+        "value": gteps,
+        "unit": "GTEPS",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "bool",
+        "data": "synthetic (Graph500-style R-MAT .57/.19/.19/.05, generated on device, seed 42)",
+        "config": {"workload": f"level-BFS q<!v.S,replace> = q {args.semiring.replace('_', '.')} A "
+                               f"({'GxB_ANY_PAIR_BOOL' if args.semiring == 'any_pair' else 'GrB_LOR_LAND_SEMIRING_BOOL'}"
+                               f"; GrB_vxm, GrB_mxv on A^T "
+                               f"shards for N>1), R-MAT scale {scale}, edge factor {args.edge_factor}, "
+                               f"16 roots", "n": n, "nnz": nnz,
+                   "parallelism": (f"1-D row shards x{world}, frontier exchange: "
+                                   f"{'device-initiated peer windows' if peerx else 'all-gather'}"
+                                   + (f" ({exchange_note})" if exchange_note else ""))
+                   if world > 1 else "single GPU"},
+        "gteps_harmonic_mean": hm,
+        "ingest_s": ingest_s,
+    }
+
+    def finish():
+        if peerx is not None:
+            peerx.check()  # raises if a wait timed out (a peer never arrived): no line is printed then
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if peerx is not None:
+            peerx.free()
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        return finish()
 
     # roofline pass (after the timed region): HIP events on the library stream around
     # every GrB_vxm / GrB_mxv (k_dir_prep + k_iso_work), one BFS per root
@@ -1273,31 +1353,8 @@ def main():
         cpu["graphblas_loop_1thread"] = {"value": done1 / t1_cpu / 1e9, "unit": "GTEPS", "cores": 1,
                                          "sample": f"{runs1} roots, {t1_cpu:.1f} s"}
 
-    if peerx is not None:
-        peerx.check()  # raises if a wait timed out (a peer never arrived): no line is printed then
     if rank == 0:
-        out = {
-            "metric": "GTEPS (masked mxv/vxm level-BFS, R-MAT s22)",
-            "value": gteps,
-            "unit": "GTEPS",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "bool",
-            "data": "synthetic (Graph500-style R-MAT .57/.19/.19/.05, generated on device, seed 42)",
-            "config": {"workload": f"level-BFS q<!v.S,replace> = q {args.semiring.replace('_', '.')} A "
-                                   f"({'GxB_ANY_PAIR_BOOL' if args.semiring == 'any_pair' else 'GrB_LOR_LAND_SEMIRING_BOOL'}"
-                                   f"; GrB_vxm, GrB_mxv on A^T "
-                                   f"shards for N>1), R-MAT scale {scale}, edge factor {args.edge_factor}, "
-                                   f"16 roots", "n": n, "nnz": nnz,
-                       "parallelism": (f"1-D row shards x{world}, frontier exchange: "
-                                       f"{'device-initiated peer windows' if peerx else 'all-gather'}"
-                                       + (f" ({exchange_note})" if exchange_note else ""))
-                       if world > 1 else "single GPU"},
+        out.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
                          "frac": (achieved / PEAK_HBM_GBS) if achieved else None, "traffic": traffic,
                          "traffic_source": os.path.relpath(args.traffic_file, ROOT) if traffic else None,
@@ -1313,18 +1370,11 @@ def main():
                          if trace_us else None,
                          "launches": launches, "alg_bytes_per_launch": alg_bytes / launches,
                          "stream_copy_GBs": copy_gbs},
-            "gteps_harmonic_mean": hm,
             "cpu_baseline": cpu,
             "parity_vs_oracle": parity,
-            "ingest_s": ingest_s,
             "secondary": secondary,
-        }
-        print(json.dumps(out), flush=True)
-    if peerx is not None:
-        peerx.free()
-    if dist:
-        dist.barrier()
-        dist.destroy_process_group()
+        })
+    finish()
 
 
 if __name__ == "__main__":

@@ -13,7 +13,7 @@ import sys
 
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r01"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(root, "gpurun_out")
+src = os.environ.get("OUT_DIR") or os.path.join(root, "out")  # where tools/collect_profiles.sh wrote
 dst = os.path.join(root, "profiles")
 os.makedirs(dst, exist_ok=True)
 shutil.copy(os.path.join(src, "prof_stats", "bench_kernel_stats.csv"), os.path.join(dst, f"{rnd}_bench_kernel_stats.csv"))
