@@ -304,6 +304,39 @@ __device__ __forceinline__ int gb_wlist_find(const gb_wlist &L, int n, int e) {
     return lo;
 }
 
+// pull: after a round's walk, rows that hit set their bit in hitw; the survivors (no hit, edges
+// left) are compacted in place (chunks of 64, in order); returns how many survive
+__device__ __forceinline__ int gb_wlist_survivors(gb_wlist &L, int n, int lane, unsigned long long lt) {
+    int m = 0;
+    for (int c0 = 0; c0 < n; c0 += 64) {
+        const int i = c0 + lane;
+        bool alive = false, hit = false;
+        int64_t np = 0;
+        int32_t nr = 0;
+        int16_t id = 0;
+        if (i < n) {
+            const int32_t taken = L.pref[i] - gb_wlist_start(L, i);
+            hit = L.hit[i] != 0;
+            id = L.id[i];
+            np = L.p[i] + taken;
+            nr = L.rem[i] - taken;
+            alive = !hit && nr > 0;
+        }
+        if (hit) atomicOr(&L.hitw[id >> 6], 1ULL << (id & 63));
+        const unsigned long long ab = __ballot(alive);
+        gb_wave_sync();
+        if (alive) {
+            const int j = m + __popcll(ab & lt);
+            L.p[j] = np;
+            L.rem[j] = nr;
+            L.id[j] = id;
+        }
+        m += __popcll(ab);
+        gb_wave_sync();
+    }
+    return m;
+}
+
 // The fused assign (gb_asg) for the 4 words w0..w0+3 of q (lanes 0-3 hold word
 // w0 + (lane & 3) in qw): w's presence words |= q, w's value at each q bit = x
 // (one lane per position: coalesced stores); returns the entries added to w.
@@ -351,7 +384,8 @@ __device__ __forceinline__ long long gb_push_phase(int64_t nwords_u, const uint6
                                                   unsigned long long *__restrict__ tbits, gb_wlist &L,
                                                   const int64_t *__restrict__ hprow, long long &mfn,
                                                   const uint64_t *__restrict__ qbits, const gb_asg_dev &g,
-                                                  long long &adelta, bool serial = false, bool prefetch = true) {
+                                                  long long &adelta, bool serial = false, bool prefetch = true,
+                                                  bool defer = false) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -397,7 +431,33 @@ __device__ __forceinline__ long long gb_push_phase(int64_t nwords_u, const uint6
             }
         }
     }
-    // frontier words, 4 per wave step (lanes 0-3 load them; the first 16 steps' came above)
+    // the wave's segment list walked as one edge stream, then emptied
+    int n = 0;
+    auto flush = [&]() {
+        gb_wave_sync();
+        const int total = gb_wlist_round(L, n, 1 << 30, lane);
+        for (int e0 = 0; e0 < total; e0 += 256) {
+            int32_t j[4];
+            bool ok[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int e = e0 + lane + 64 * u;
+                ok[u] = e < total;
+                j[u] = 0;
+                if (ok[u]) {
+                    const int s = gb_wlist_find(L, n, e);
+                    j[u] = pcol[L.p[s] + (e - gb_wlist_start(L, s))];
+                }
+            }
+            added += gb_push_targets(j, ok, mbits, mcomp, tbits, hprow, mfn, qbits, serial);
+        }
+        gb_wave_sync();
+        n = 0;
+    };
+    // frontier words, 4 per wave step (lanes 0-3 load them; the first 16 steps' came above).
+    // defer (knob iso_pack): the rows of successive steps pile up in the list, which is walked
+    // only when the next step's rows would not fit or the words are exhausted -- one chain of
+    // edge / mask / output reads for a sparse frontier's few rows per step instead of one per step
     int step = 0;
     for (int64_t w0 = wave * 4; w0 < nwords_u; w0 += nwaves * 4, step++) {
         const int64_t wl = w0 + (lane & 3);
@@ -420,38 +480,27 @@ __device__ __forceinline__ long long gb_push_phase(int64_t nwords_u, const uint6
                 d[u] = prow[k + 1] - p0[u];
             }
         }
-        int n = 0;
+        unsigned long long bb[4];
+        int add = 0;
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            const bool in = d[u] > 0 && d[u] <= H;  // hubs: done by their chunks
-            const unsigned long long bb = __ballot(in);
-            if (in) {
-                const int i = n + __popcll(bb & lt);
+            bb[u] = __ballot(d[u] > 0 && d[u] <= H);  // hubs: done by their chunks
+            add += __popcll(bb[u]);
+        }
+        if (!add) continue;
+        if (n + add > WL_MAX) flush();  // a step has at most 256 rows: it fits an empty list
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            if ((bb[u] >> lane) & 1ULL) {
+                const int i = n + __popcll(bb[u] & lt);
                 L.p[i] = p0[u];
                 L.rem[i] = (int32_t)d[u];
             }
-            n += __popcll(bb);
+            n += __popcll(bb[u]);
         }
-        if (!n) continue;
-        gb_wave_sync();
-        const int total = gb_wlist_round(L, n, 1 << 30, lane);
-        for (int e0 = 0; e0 < total; e0 += 256) {
-            int32_t j[4];
-            bool ok[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const int e = e0 + lane + 64 * u;
-                ok[u] = e < total;
-                j[u] = 0;
-                if (ok[u]) {
-                    const int s = gb_wlist_find(L, n, e);
-                    j[u] = pcol[L.p[s] + (e - gb_wlist_start(L, s))];
-                }
-            }
-            added += gb_push_targets(j, ok, mbits, mcomp, tbits, hprow, mfn, qbits, serial);
-        }
-        gb_wave_sync();
+        if (!defer) flush();
     }
+    if (n) flush();
     return added;
 }
 
@@ -690,35 +739,7 @@ __device__ __forceinline__ long long gb_pull_iso_phase(int64_t nrows, const int6
                     if (ok[u] && gb_bit(ubits, k[u])) L.hit[s[u]] = 1;
             }
             gb_wave_sync();
-            // survivors of the round, compacted in place (chunks of 64, in order)
-            int m = 0;
-            for (int c0 = 0; c0 < n; c0 += 64) {
-                const int i = c0 + lane;
-                bool alive = false, hit = false;
-                int64_t np = 0;
-                int32_t nr = 0;
-                int16_t id = 0;
-                if (i < n) {
-                    const int32_t taken = L.pref[i] - gb_wlist_start(L, i);
-                    hit = L.hit[i] != 0;
-                    id = L.id[i];
-                    np = L.p[i] + taken;
-                    nr = L.rem[i] - taken;
-                    alive = !hit && nr > 0;
-                }
-                if (hit) atomicOr(&L.hitw[id >> 6], 1ULL << (id & 63));
-                const unsigned long long ab = __ballot(alive);
-                gb_wave_sync();
-                if (alive) {
-                    const int j = m + __popcll(ab & lt);
-                    L.p[j] = np;
-                    L.rem[j] = nr;
-                    L.id[j] = id;
-                }
-                m += __popcll(ab);
-                gb_wave_sync();
-            }
-            n = m;
+            n = gb_wlist_survivors(L, n, lane, lt);
             cap = cap < (1 << 20) ? cap * 2 : cap;
         }
         gb_wave_sync();
@@ -739,6 +760,210 @@ __device__ __forceinline__ long long gb_pull_iso_phase(int64_t nrows, const int6
             for (int u = 0; u < PULL_U; u++)
                 if (found[u]) mfn += dg[u];
         }
+    }
+    return cnt;
+}
+
+// The pull with its open rows packed (knob iso_pack; needs the pull heads, no lane-per-row
+// steps).  The loop above pays its chain of dependent reads (control words, heads, probes, row
+// bounds, edges, frontier bits) once per step of 4 words = 256 lane slots, most of them closed
+// by the mask or empty.  Here a wave takes its words in groups of PACK_G steps: one lane owns
+// one word and one round trip loads the group's control words; the open rows are packed by a
+// prefix sum of the words' popcounts into a per-wave LDS list and the chain runs once per batch
+// of 256 packed rows.  Found flags go back through LDS words to the lanes that own the output
+// words.  Same rows, same probes, same list rounds: results, count, stamp and hint are those of
+// the loop above.  Every loop is bounded by counts in registers (groups, batches, list rounds).
+#define PACK_G 4                  // steps per group
+#define PACK_W (PACK_G * PULL_U)  // words per group, one lane each
+struct gb_wpack {
+    int16_t ids[PACK_W * 64];           // the group's open rows in order: word in group * 64 + bit
+    unsigned long long fw[PACK_W];      // found flags of the packed slots, 64 per word
+};
+__device__ __forceinline__ long long gb_pull_iso_packed(int64_t nrows, const int64_t *__restrict__ rowptr,
+                                                       const int32_t *__restrict__ colidx,
+                                                       const uint64_t *__restrict__ ubits,
+                                                       const uint64_t *__restrict__ mbits, bool mcomp,
+                                                       uint64_t *__restrict__ tbits, gb_wlist &L, gb_wpack &P,
+                                                       const int64_t *__restrict__ hprow, long long &mfn, int cap0,
+                                                       const uint64_t *__restrict__ rne,
+                                                       const uint64_t *__restrict__ qbits, const gb_asg_dev &g,
+                                                       long long &adelta, const int32_t *__restrict__ ph,
+                                                       const uint32_t *__restrict__ pdeg) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t nwords = (nrows + 63) >> 6;
+    const int64_t stride = nwaves * PULL_U;  // words between a wave's steps
+    const uint64_t tail = (nrows & 63) ? ((1ULL << (nrows & 63)) - 1) : ~0ULL;
+    const unsigned long long lt = (1ULL << lane) - 1;
+    long long cnt = 0;
+    for (int64_t wb = wave * PULL_U; wb < nwords; wb += stride * PACK_G) {
+        // lane l < PACK_W owns word l % PULL_U of the group's step l / PULL_U (as the push's `pre`)
+        const int64_t wl = wb + (int64_t)(lane / PULL_U) * stride + (lane & (PULL_U - 1));
+        const bool inr = lane < PACK_W && wl < nwords;
+        const uint64_t qw = (qbits && inr) ? qbits[wl] : 0;
+        const uint64_t mw = (mbits && inr) ? mbits[wl] : 0;
+        const uint64_t rw = (rne && inr) ? rne[wl] : ~0ULL;
+        uint64_t mine = ~0ULL;
+        if (qbits) {  // fused assign (gb_asg_words): w |= q, w's value at each q bit = x
+            if (qw) {
+                const uint64_t c = g.bits == mbits ? mw : g.bits[wl], nwd = c | qw;
+                if (nwd != c) g.bits[wl] = nwd;
+                adelta += (long long)__popcll(nwd) - (long long)__popcll(c);
+            }
+            for (unsigned long long qb = __ballot(qw != 0); qb; qb &= qb - 1) {
+                const int u = __ffsll(qb) - 1;
+                const uint64_t word = __shfl(qw, u, 64);
+                const int64_t wu = wb + (int64_t)(u / PULL_U) * stride + (u & (PULL_U - 1));
+                if ((word >> lane) & 1ULL) gb_store_sized(g.vals, (wu << 6) + lane, g.size, g.x);
+            }
+            if (mbits) mine = mcomp ? ~(mw | qw) : (mw | qw);
+        } else if (mbits) {
+            mine = mcomp ? ~mw : mw;
+        }
+        if (rne) mine &= rw;  // rows without entries produce nothing
+        if (wl == nwords - 1) mine &= tail;
+        if (!inr) mine = 0;
+        // each word's first packed slot: exclusive prefix of the popcounts over the owning lanes
+        const int c = __popcll(mine);
+        int incl = c;
+#pragma unroll
+        for (int off = 1; off < PACK_W; off <<= 1) {
+            const int y = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += y;
+        }
+        const int excl = incl - c;
+        const int total = __shfl(incl, PACK_W - 1, 64);
+        if (!total) {  // nothing open in the group
+            if (inr) tbits[wl] = 0;
+            continue;
+        }
+        const unsigned long long ob = __ballot(mine != 0);
+        for (unsigned long long b = ob; b; b &= b - 1) {
+            const int u = __ffsll(b) - 1;
+            const uint64_t word = __shfl(mine, u, 64);
+            const int base = __shfl(excl, u, 64);
+            if ((word >> lane) & 1ULL) P.ids[base + __popcll(word & lt)] = (int16_t)(u * 64 + lane);
+        }
+        gb_wave_sync();
+        for (int b0 = 0; b0 < total; b0 += 256) {
+            bool live[PULL_U], found[PULL_U];
+            int64_t r[PULL_U];
+            int4 hv[PULL_U];
+#pragma unroll
+            for (int u = 0; u < PULL_U; u++) {
+                const int i = b0 + u * 64 + lane;
+                live[u] = i < total;
+                const int id = live[u] ? P.ids[i] : 0;
+                r[u] = ((wb + (int64_t)(id >> 8) * stride + ((id >> 6) & (PULL_U - 1))) << 6) + (id & 63);
+                hv[u] = make_int4(-1, -1, -1, -1);
+                if (live[u]) hv[u] = reinterpret_cast<const int4 *>(ph)[r[u]];
+            }
+            // the head probes in two rounds, as in the loop above
+            const uint32_t *ub32 = reinterpret_cast<const uint32_t *>(ubits);
+            uint32_t w1[PULL_U];
+#pragma unroll
+            for (int u = 0; u < PULL_U; u++) {
+                w1[u] = 0;
+                if (hv[u].x >= 0) w1[u] = ub32[hv[u].x >> 5];
+            }
+#pragma unroll
+            for (int u = 0; u < PULL_U; u++) found[u] = hv[u].x >= 0 && ((w1[u] >> (hv[u].x & 31)) & 1u);
+            uint32_t wy[PULL_U], wz[PULL_U], ww[PULL_U];
+#pragma unroll
+            for (int u = 0; u < PULL_U; u++) {
+                wy[u] = wz[u] = ww[u] = 0;
+                if (!found[u]) {
+                    if (hv[u].y >= 0) wy[u] = ub32[hv[u].y >> 5];
+                    if (hv[u].z >= 0) wz[u] = ub32[hv[u].z >> 5];
+                    if (hv[u].w >= 0) ww[u] = ub32[hv[u].w >> 5];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < PULL_U; u++)
+                found[u] = found[u] || (hv[u].y >= 0 && ((wy[u] >> (hv[u].y & 31)) & 1u)) ||
+                           (hv[u].z >= 0 && ((wz[u] >> (hv[u].z & 31)) & 1u)) ||
+                           (hv[u].w >= 0 && ((ww[u] >> (hv[u].w & 31)) & 1u));
+            int64_t p[PULL_U], p1[PULL_U], dg[PULL_U];
+#pragma unroll
+            for (int u = 0; u < PULL_U; u++) {
+                p[u] = p1[u] = 0;
+                if (live[u] && !found[u] && hv[u].w == -2 && r[u] < nrows) {  // a long row: walk it
+                    p[u] = rowptr[r[u]];
+                    p1[u] = rowptr[r[u] + 1];
+                }
+                dg[u] = (hprow && found[u]) ? (int64_t)pdeg[r[u]] : p1[u] - p[u];
+            }
+            // rows still open -> segment list (ids local to the batch: u * 64 + lane)
+            int n = 0;
+#pragma unroll
+            for (int u = 0; u < PULL_U; u++) {
+                const bool pd = p[u] < p1[u];
+                const unsigned long long bb = __ballot(pd);
+                if (pd) {
+                    const int i = n + __popcll(bb & lt);
+                    L.p[i] = p[u];
+                    L.rem[i] = (int32_t)(p1[u] - p[u]);
+                    L.id[i] = (int16_t)(u * 64 + lane);
+                }
+                n += __popcll(bb);
+            }
+            if (lane < PULL_U) L.hitw[lane] = 0;
+            int cap = cap0;
+            while (n) {
+                gb_wave_sync();
+                const int tot = gb_wlist_round(L, n, cap, lane);
+                for (int e0 = 0; e0 < tot; e0 += 256) {
+                    int k[4], s[4];
+                    bool ok[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) {
+                        const int e = e0 + lane + 64 * u;
+                        ok[u] = e < tot;
+                        s[u] = 0;
+                        k[u] = 0;
+                        if (ok[u]) {
+                            s[u] = gb_wlist_find(L, n, e);
+                            k[u] = colidx[L.p[s[u]] + (e - gb_wlist_start(L, s[u]))];
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; u++)
+                        if (ok[u] && gb_bit(ubits, k[u])) L.hit[s[u]] = 1;
+                }
+                gb_wave_sync();
+                n = gb_wlist_survivors(L, n, lane, lt);
+                cap = cap < (1 << 20) ? cap * 2 : cap;
+            }
+            gb_wave_sync();
+#pragma unroll
+            for (int u = 0; u < PULL_U; u++) {
+                if ((L.hitw[u] >> lane) & 1ULL) found[u] = true;
+                const unsigned long long word = __ballot(found[u]);
+                if (lane == 0) P.fw[(b0 >> 6) + u] = word;
+                if (hprow && found[u]) mfn += dg[u];  // the hint, as in the loop above
+            }
+            gb_wave_sync();
+        }
+        // scatter-back: each open row reads its slot's flag; the owning lane stores the word
+        unsigned long long res = 0;
+        for (unsigned long long b = ob; b; b &= b - 1) {
+            const int u = __ffsll(b) - 1;
+            const uint64_t word = __shfl(mine, u, 64);
+            const int base = __shfl(excl, u, 64);
+            bool f = false;
+            if ((word >> lane) & 1ULL) {
+                const int i = base + __popcll(word & lt);
+                f = (P.fw[i >> 6] >> (i & 63)) & 1ULL;
+            }
+            const unsigned long long fb = __ballot(f);
+            if (lane == u) res = fb;
+        }
+        if (inr) {
+            tbits[wl] = res;
+            cnt += __popcll(res);
+        }
+        gb_wave_sync();
     }
     return cnt;
 }
@@ -803,6 +1028,7 @@ struct gb_iso_args {
                                     // 16 pull without its segment list, 32 pull steps without probes (wrong results),
                                     // 64 no finish, 128 the round-4 dependent read order (exact; A/B),
                                     // 512 push without the frontier-word prefetch (exact; A/B)
+    int pack;                       // open rows packed across a wave's steps (knob iso_pack): 1 pull, 2 push
     bool packed;                    // one-round finish (iso_finish_packed): n < 2^27
     const uint64_t *rows_nonempty;  // pull rows with entries (nullptr: all)
     const int32_t *phead;           // pull head per row, 4 int32 (nullptr: none; gb_view_pullfirst)
@@ -1331,6 +1557,7 @@ __global__ __launch_bounds__(SPMV_BLOCK) void k_iso_work(
     unsigned long long *__restrict__ tcount, unsigned long long *__restrict__ gst, gb_iso_args a) {
     __shared__ gb_wlist lists[WAVES_PER_BLOCK];
     gb_wlist &L = lists[threadIdx.x >> 6];
+    __shared__ gb_wpack packs[WAVES_PER_BLOCK];
     if (a.ts && blockIdx.x == 0 && threadIdx.x == 0) iso_ts_mark(a, 0);
     if (a.dbg & 8) return;  // diagnostics: the launch alone
     bool push = false;
@@ -1387,11 +1614,16 @@ __global__ __launch_bounds__(SPMV_BLOCK) void k_iso_work(
     else if (push)
         cnt = gb_push_phase(nwords_u, ubits, prow, pcol, hubs, nhubs, H, mbits, mcomp,
                             (unsigned long long *)tbits, L, a.hprow, mfn, qbits, a.asg, adelta, (a.dbg & 128) != 0,
-                            (a.dbg & 512) == 0);
-    else
-        cnt = gb_pull_iso_phase(nrows, rowptr, colidx, ubits, mbits, mcomp, tbits, L, a.hprow, mfn, a.p1_steps,
-                                a.cap0, a.rows_nonempty, qbits, a.asg, adelta, a.dbg,
-                                (a.phead && (!a.hprow || a.pdeg)) ? a.phead : nullptr, a.pdeg);
+                            (a.dbg & 512) == 0, (a.pack & 2) != 0);
+    else {
+        const int32_t *ph = (a.phead && (!a.hprow || a.pdeg)) ? a.phead : nullptr;
+        if ((a.pack & 1) && ph && a.p1_steps == 0 && !(a.dbg & (16 | 32 | 128)))
+            cnt = gb_pull_iso_packed(nrows, rowptr, colidx, ubits, mbits, mcomp, tbits, L, packs[threadIdx.x >> 6],
+                                     a.hprow, mfn, a.cap0, a.rows_nonempty, qbits, a.asg, adelta, ph, a.pdeg);
+        else
+            cnt = gb_pull_iso_phase(nrows, rowptr, colidx, ubits, mbits, mcomp, tbits, L, a.hprow, mfn, a.p1_steps,
+                                    a.cap0, a.rows_nonempty, qbits, a.asg, adelta, a.dbg, ph, a.pdeg);
+    }
     if (a.dbg & 64) return;  // diagnostics: no finish (count, hint, mailbox)
     if (a.packed) {
         iso_finish_packed(cnt, mfn, adelta, tcount, gst, a);
@@ -1736,6 +1968,10 @@ void gb_spmv(gb_vec_result &T, const gb_csr_view &A, const gb_csr_view *Apush, g
                 args.asg_count = (unsigned long long *)asg->count;
             }
             args.dbg = (int)gb_knob("iso_dbg");
+            // open rows packed across a wave's steps: 0 pull and push (default), 1 neither (the
+            // per-step loops), 2 pull only, 3 push only
+            const int64_t pack_knob = gb_knob("iso_pack");
+            args.pack = ((pack_knob == 0 || pack_knob == 2) ? 1 : 0) | ((pack_knob == 0 || pack_knob == 3) ? 2 : 0);
             args.ts = iso_ts_buffer();
             args.root = asg ? asg->root : -1;
             GB_REQUIRE(args.root < 0 || can_push, GrB_PANIC, "a pending root needs the push orientation");

@@ -79,12 +79,16 @@ static void spmv_build_views(spmv_views &V, GB_Obj *mask, GrB_Semiring sr, GB_Ob
     V.uv.full = u->kind != GB_KIND_MATRIX && u->nvals_valid && u->nvals == u->nrows && u->nrows > 0;
     if (!V.iso_result && V.uv.full && !V.uv.iso && A->kind == GB_KIND_MATRIX && !gb_sr_describe(sr).positional)
         gb_view_hot(V.av, A, use_csc ? 1 : 0);
-    if (A->kind == GB_KIND_MATRIX && gb_knob("spmv_direction") != 1 && V.iso_result) {
+    // (pull only, spmv_direction 1: no push, but the pull keeps its heads -- the pull it forces is
+    // the default's pull, packed rows included)
+    if (A->kind == GB_KIND_MATRIX && V.iso_result) {
         if (use_csc) gb_get_csr(V.pv, A);
         else gb_get_csc(V.pv, A);
-        int64_t H = gb_knob("push_heavy");
-        gb_view_hubs(V.pv, A, use_csc ? 0 : 1, H > 0 ? H : 512);
-        V.push = &V.pv;
+        if (gb_knob("spmv_direction") != 1) {
+            int64_t H = gb_knob("push_heavy");
+            gb_view_hubs(V.pv, A, use_csc ? 0 : 1, H > 0 ? H : 512);
+            V.push = &V.pv;
+        }
         if (gb_knob("pull_first") != 1) gb_view_pullfirst(V.av, A, use_csc ? 1 : 0, V.pv.rowptr, V.pv.nrows);
     }
 }

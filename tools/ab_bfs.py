@@ -97,5 +97,5 @@ for rnd in range(rounds):
 for s in settings:
     t = np.array(res[s])
     per = np.array(lev[s]).min(axis=0)
-    print(f"[{s or 'defaults'}] ms/BFS median {np.median(t):.4f} min {t.min():.4f} | root7 levels us "
+    print(f"[{s or 'defaults'}] ms/BFS median {np.median(t):.4f} min {t.min():.4f} max {t.max():.4f} | root7 levels us "
           + " ".join(f"{x:.1f}" for x in per), flush=True)
