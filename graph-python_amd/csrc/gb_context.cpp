@@ -594,6 +594,10 @@ GrB_Info GrB_UnaryOp_free(GrB_UnaryOp *op) {
     (void)op;
     return GrB_SUCCESS;
 }
+GrB_Info GrB_IndexUnaryOp_free(GrB_IndexUnaryOp *op) {
+    (void)op;
+    return GrB_SUCCESS;
+}
 GrB_Info GxB_Semiring_add(GrB_Monoid *add, GrB_Semiring s) {
     if (!add || !s) return GrB_NULL_POINTER;
     *add = s->add;

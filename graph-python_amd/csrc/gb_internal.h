@@ -41,6 +41,12 @@ struct GB_UnaryOp_opaque {
     GrB_Type xtype, ztype;
     const char *name;
 };
+struct GB_IndexUnaryOp_opaque {
+    uint64_t magic;
+    int opcode;
+    GrB_Type xtype, ytype;  // xtype == nullptr: positional op (thunk INT64)
+    const char *name;
+};
 struct GB_Monoid_opaque {
     uint64_t magic;
     int mcode;
@@ -554,6 +560,11 @@ void gb_spgemm(gb_mat_result &T, gb_csr_view &A, gb_csr_view &B, gb_csr_view *BT
 // the pool.  Returns false (nothing changed but the old bitmap possibly taken) when the pool
 // has nothing of this size: the caller then allocates and zeroes as usual.
 bool gb_zpool_clear_vector(GB_Obj *v);
+
+// select (gb_select.hip): T = the entries of A' the index-unary operator keeps for the thunk
+// *y (type ycode), written back as C<M> = C accum T
+void gb_select(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_IndexUnaryOp op, GB_Obj *A, const void *y, int ycode,
+               const gb_desc &d);
 
 // hash Gustavson C = A*B (gb_spgemm_hash.hip): flops = per-row product counts
 void gb_spgemm_hash(gb_mat_result &T, gb_csr_view &A, gb_csr_view &B, GrB_Semiring sr, bool iso,

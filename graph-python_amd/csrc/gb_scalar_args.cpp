@@ -8,6 +8,8 @@
 //   GrB_{Vector,Matrix}_apply_BinaryOp{1st,2nd}_Scalar
 //                                              reference core/vector.py:1406,1449,
 //                                              core/matrix.py:2392,2435
+//   GrB_{Vector,Matrix}_select_Scalar          reference core/vector.py:1463-1560,
+//                                              core/matrix.py:2452-2551
 // Each reads the scalar's value (its own type) on the host and forwards to the typed entry
 // point of that type, which casts it as the typed call would.  An empty GrB_Scalar means
 // "no value" (C API 2.0): setElement deletes the entry; extractElement of a missing entry
@@ -169,6 +171,28 @@ GrB_Info apply_scalar(bool vec, bool first, OUT w, const OUT mask, const GrB_Bin
     }
     return GrB_DOMAIN_MISMATCH;
 }
+
+// select with the thunk in a GrB_Scalar
+template <class OUT>
+GrB_Info select_scalar(bool vec, OUT w, const OUT mask, const GrB_BinaryOp accum, const GrB_IndexUnaryOp op,
+                       const OUT u, const GrB_Scalar s, const GrB_Descriptor desc) {
+    sval v;
+    GrB_Info e = read_scalar(v, s);
+    if (e != GrB_SUCCESS) return e;
+    if (!v.present) return fail_on(w, GrB_EMPTY_OBJECT, "select: the thunk GrB_Scalar holds no value");
+    switch (v.code) {
+#define GB_SELECT(T, ctype)                                                                               \
+    case GBAMD_T_##T: {                                                                                   \
+        ctype c;                                                                                          \
+        std::memcpy(&c, v.bytes, sizeof(ctype));                                                          \
+        if (vec) return GrB_Vector_select_##T((GrB_Vector)w, (GrB_Vector)mask, accum, op, (GrB_Vector)u, c, desc); \
+        return GrB_Matrix_select_##T((GrB_Matrix)w, (GrB_Matrix)mask, accum, op, (GrB_Matrix)u, c, desc); \
+    }
+        GB_FOR_EACH_TYPE(GB_SELECT)
+#undef GB_SELECT
+    }
+    return GrB_DOMAIN_MISMATCH;
+}
 }  // namespace
 
 extern "C" {
@@ -291,6 +315,17 @@ GrB_Info GrB_Matrix_apply_BinaryOp2nd_Scalar(GrB_Matrix C, const GrB_Matrix Mask
                                              const GrB_BinaryOp op, const GrB_Matrix A, const GrB_Scalar y,
                                              const GrB_Descriptor desc) {
     return apply_scalar(false, false, C, Mask, accum, op, y, A, desc);
+}
+
+GrB_Info GrB_Vector_select_Scalar(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum,
+                                  const GrB_IndexUnaryOp op, const GrB_Vector u, const GrB_Scalar y,
+                                  const GrB_Descriptor desc) {
+    return select_scalar(true, w, mask, accum, op, u, y, desc);
+}
+GrB_Info GrB_Matrix_select_Scalar(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum,
+                                  const GrB_IndexUnaryOp op, const GrB_Matrix A, const GrB_Scalar y,
+                                  const GrB_Descriptor desc) {
+    return select_scalar(false, C, Mask, accum, op, A, y, desc);
 }
 
 }  // extern "C"

@@ -22,7 +22,7 @@ from .exceptions import (DimensionMismatch, DomainMismatch, EmptyObject, Graphbl
                          NotImplementedException, NoValue, NullPointer, OutOfMemory, OutputNotEmpty,
                          Panic, UninitializedObject)
 from .matrix import Matrix, MatrixExpression, TransposedMatrix
-from .operator import binary, monoid, op, semiring, unary
+from .operator import binary, indexunary, monoid, op, select, semiring, unary
 from .scalar import Scalar, ScalarExpression
 from .vector import Vector, VectorExpression
 
@@ -70,7 +70,7 @@ def wait():
 
 
 __all__ = ["Matrix", "Vector", "Scalar", "TransposedMatrix", "Recorder", "binary", "monoid", "semiring",
-           "op", "unary", "agg", "dtypes", "init", "replace", "backend", "lib"]
+           "op", "unary", "select", "indexunary", "agg", "dtypes", "init", "replace", "backend", "lib"]
 
 from . import dtypes  # noqa: E402
 from . import io  # noqa: E402,F401

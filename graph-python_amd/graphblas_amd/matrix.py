@@ -322,6 +322,9 @@ class Matrix(BaseType):
     def apply(self, op, right=None, *, left=None):
         return _apply_expr(self, op, right, left)
 
+    def select(self, op, thunk=None):
+        return _select_expr(self, op, thunk)
+
     def isequal(self, other, *, check_dtype=False):
         """reference core/matrix.py:357-398"""
         if isinstance(other, TransposedMatrix):
@@ -529,6 +532,9 @@ class TransposedMatrix:
     def apply(self, op, right=None, *, left=None):
         return _apply_expr(self, op, right, left)
 
+    def select(self, op, thunk=None):
+        return _select_expr(self, op, thunk)
+
     def to_coo(self, *args, **kw):
         r, c, v = self._matrix.to_coo(*args, **kw)
         o = np.lexsort((r, c))
@@ -646,6 +652,67 @@ def _apply_expr(x, op, right, left):
     if right is None:
         return mk(f"GrB_{kind}_apply_BinaryOp1st_{sc.dtype.name}", [cv, src], t)
     return mk(f"GrB_{kind}_apply_BinaryOp2nd_{sc.dtype.name}", [src, cv], t)
+
+
+def _select_mask(updater, obj, mask):
+    """x.select(mask): the entries of x the mask selects (reference core/vector.py:80-93)."""
+    from .base import Updater
+
+    if updater.mask is None:
+        Updater(updater.parent, mask=mask, accum=updater.accum, replace=updater.accum is None,
+                opts=updater.opts) << obj
+    else:
+        updater << obj.dup(mask=mask)
+
+
+def _select_expr(x, op, thunk):
+    """x.select(op, thunk) (reference core/vector.py:1463-1560, core/matrix.py:2452-2551): the
+    entries a SelectOp keeps -> GrB_*_select_<T> (a Scalar thunk: GrB_*_select_Scalar); a mask in
+    place of the operator -> the entries it selects."""
+    from .base import Mask
+    from .scalar import Scalar
+    from .vector import Vector, VectorExpression
+
+    kind = "Vector" if x.ndim == 1 else "Matrix"
+    src, at = _unwrap(x) if kind == "Matrix" else (x, False)
+
+    def mk(cf, args, t=None):
+        if kind == "Vector":
+            return VectorExpression("select", cf, args, op=t, size=x.size, dtype=x.dtype)
+        return MatrixExpression("select", cf, args, op=t, at=at if cf else False, nrows=x.nrows, ncols=x.ncols,
+                                dtype=x.dtype)
+
+    if isinstance(op, (Mask, Matrix, Vector)):
+        if thunk is not None:
+            raise TypeError("thunk argument not None when calling select with mask or boolean object")
+        mask = _check_mask(op)
+        if type(mask.parent) is not (Vector if kind == "Vector" else Matrix):
+            raise TypeError(f"Bad type for argument `op` in select: expected a {kind} mask, got "
+                            f"{type(mask.parent).__name__}")
+        obj = x.new() if at else x
+        return mk(None, [obj, mask, _select_mask, (obj, mask)])
+    if thunk is None:
+        thunk = False  # the most basic form of 0 when unifying dtypes
+    if isinstance(thunk, Scalar):
+        tdtype, cf, arg = thunk.dtype, f"GrB_{kind}_select_Scalar", thunk
+    else:
+        # a literal: a C scalar of its numpy type, handed to the typed entry point (no GrB_Scalar)
+        try:
+            a = np.asarray(thunk)
+            if a.ndim != 0:
+                raise TypeError("not a scalar")
+            tdtype = lookup_dtype(a.dtype)
+        except (TypeError, ValueError) as exc:
+            raise TypeError(f"Bad type for keyword argument `thunk` in select: {type(thunk)}; expected a "
+                            "Scalar or a literal scalar") from exc
+        arg, cf = a.item(), f"GrB_{kind}_select_{tdtype.name}"
+    t = _op.get_typed_op(op, x.dtype, tdtype, kind="select", is_right_scalar=True)
+    if t.opclass != "SelectOp":
+        raise TypeError(f"Bad type for argument `op` in select: expected SelectOp, got {t.opclass}")
+    if t.is_positional and not isinstance(thunk, Scalar):
+        # the library casts the thunk of a positional operator to INT64
+        arg, cf = int(arg), f"GrB_{kind}_select_INT64"
+    return mk(cf, [src, arg], t)
 
 
 def _unwrap(x):

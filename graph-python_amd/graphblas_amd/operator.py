@@ -91,6 +91,42 @@ class UnaryOp(OpBase):
     opclass = "UnaryOp"
 
 
+class TypedSelectOp(TypedOp):
+    """One dtype's view of a SelectOp; the positional ones all point at the one untyped object."""
+
+    __slots__ = ()
+
+    def __call__(self, expr, thunk=None):
+        return _call_select(self, expr, thunk)
+
+    def __reduce__(self):
+        return (_select_lookup, (self.parent.name, self.type.name))
+
+
+class SelectOp(OpBase):
+    """A GrB_IndexUnaryOp used as a filter (reference core/operator/select.py,
+    core/operator/indexunary.py:98-114): select.tril(A, -1) is A.select(select.tril, -1)."""
+
+    opclass = "SelectOp"
+
+    def __call__(self, expr, thunk=None):
+        return _call_select(self, expr, thunk)
+
+    def __reduce__(self):
+        return (_select_lookup, (self.name, None))
+
+
+def _select_lookup(name, dtype):
+    obj = getattr(select, name)
+    return obj if dtype is None else obj[dtype]
+
+
+def _call_select(opobj, expr, thunk):
+    if not hasattr(expr, "select"):
+        raise TypeError(f"Bad type when calling {opobj!r}: {type(expr)}")
+    return expr.select(opobj, thunk)
+
+
 class Monoid(OpBase):
     opclass = "Monoid"
 
@@ -110,6 +146,7 @@ class _Namespace(types.SimpleNamespace):
 
 binary = _Namespace()
 unary = _Namespace()
+select = _Namespace()
 monoid = _Namespace()
 semiring = _Namespace()
 
@@ -141,6 +178,18 @@ for _gb, (_op, _t) in _builtins.UNOPS.items():
     if _dt in _o._typed and _o._typed[_dt].gb_name.startswith("GrB_"):
         continue
     _o._add(TypedOp(_o, _pyname, _dt, _dt, _gb, "UnaryOp"))
+
+for _gb, (_op, _t) in _builtins.INDEXUNARYOPS.items():
+    _pyname = _op.lower()
+    _o = _get(select, SelectOp, _pyname)
+    _o.is_positional = _t is None
+    # a positional operator is defined for every dtype through its one untyped object
+    for _dt in ([lookup_dtype(_t)] if _t is not None else [lookup_dtype(t[0]) for t in _builtins.TYPES]):
+        _o._add(TypedSelectOp(_o, _pyname, _dt, BOOL, _gb, "SelectOp"))
+# the vector names of the row operators (reference core/operator/select.py)
+select.indexle = select.rowle
+select.indexgt = select.rowgt
+indexunary = _Namespace(**select.__dict__)
 
 for _gb, (_m, _t, _bop) in _builtins.MONOIDS.items():
     _pyname = "eq" if _gb == "GxB_EQ_BOOL_MONOID" else _m.lower()
@@ -279,7 +328,31 @@ _BINARY_STRINGS = {"+": "plus", "-": "minus", "*": "times", "/": "truediv", "=="
                    "^": "lxor", "min": "min", "max": "max"}
 
 
+_SELECT_STRINGS = {"<": "valuelt", ">": "valuegt", "<=": "valuele", ">=": "valuege", "!=": "valuene",
+                   "==": "valueeq", "col<=": "colle", "col>": "colgt", "row<=": "rowle", "row>": "rowgt",
+                   "index<=": "indexle", "index>": "indexgt"}
+
+
+def _select_from_string(s):
+    """reference core/operator/select.py: the comparison table, or an operator's name in any case."""
+    name = s.strip()
+    dt = None
+    if name.endswith("]") and "[" in name:
+        name, dt = name[:-1].split("[", 1)
+    name = _SELECT_STRINGS.get(name, name).lower()
+    obj = getattr(select, name, None)
+    if not isinstance(obj, SelectOp):
+        raise ValueError(f"Unknown select string: {s!r}")
+    return obj[dt] if dt else obj
+
+
+select.from_string = _select_from_string
+indexunary.from_string = _select_from_string
+
+
 def _from_string(s, kind):
+    if kind == "select":
+        return _select_from_string(s)
     name = s.strip()
     dt = None
     if name.endswith("]") and "[" in name:

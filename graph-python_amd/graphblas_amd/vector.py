@@ -13,7 +13,7 @@ from .base import (BaseExpression, BaseType, StructuralMask, ValueMask, _autonam
 from .dtypes import BOOL, FP64, lookup_dtype
 from .exceptions import DimensionMismatch, NoValue, check_status_carg
 from .matrix import Matrix, MatrixExpression, TransposedMatrix, _apply_expr, _axis_index, _binary_for, \
-    _CArray, _index_array, _reduce_scalar, _values_dtype
+    _CArray, _index_array, _reduce_scalar, _select_expr, _values_dtype
 
 
 class Vector(BaseType):
@@ -271,6 +271,9 @@ class Vector(BaseType):
 
     def apply(self, op, right=None, *, left=None):
         return _apply_expr(self, op, right, left)
+
+    def select(self, op, thunk=None):
+        return _select_expr(self, op, thunk)
 
     def isequal(self, other, *, check_dtype=False):
         if not isinstance(other, Vector):

@@ -105,6 +105,7 @@ typedef enum { GxB_MODE = 2 } GxB_Option_Field;
 typedef struct GB_Type_opaque *GrB_Type;
 typedef struct GB_BinaryOp_opaque *GrB_BinaryOp;
 typedef struct GB_UnaryOp_opaque *GrB_UnaryOp;
+typedef struct GB_IndexUnaryOp_opaque *GrB_IndexUnaryOp;
 typedef struct GB_Monoid_opaque *GrB_Monoid;
 typedef struct GB_Semiring_opaque *GrB_Semiring;
 typedef struct GB_Descriptor_opaque *GrB_Descriptor;
@@ -129,7 +130,7 @@ GrB_Info GxB_Context_get_stream(void **hip_stream);
 /* Extension: which HIP device the library uses (call before GrB_init). */
 GrB_Info GxB_Context_set_device(int device);
 /* Extension: look up a builtin object by its exported name (kind: 0 type,
- * 1 binop, 2 monoid, 3 semiring, 4 descriptor).  For FFIs that cannot read
+ * 1 binop, 2 monoid, 3 semiring, 4 descriptor, 5 unary op, 6 index-unary op).  For FFIs that cannot read
  * data symbols directly. */
 GrB_Info GxB_builtin_lookup(void **handle, int *kind, const char *name);
 /* Extension: object names for diagnostics / recorder strings. */
@@ -141,6 +142,7 @@ GrB_Info GrB_BinaryOp_free(GrB_BinaryOp *op);
 GrB_Info GrB_Monoid_free(GrB_Monoid *monoid);
 GrB_Info GrB_Semiring_free(GrB_Semiring *semiring);
 GrB_Info GrB_UnaryOp_free(GrB_UnaryOp *op);
+GrB_Info GrB_IndexUnaryOp_free(GrB_IndexUnaryOp *op);
 /* semiring from a builtin monoid and a builtin binary operator whose output type is the
  * monoid's (python-graphblas registers e.g. plus_pow this way for agg.sum_of_squares,
  * reference core/operator/agg.py:271-276) */
@@ -199,7 +201,10 @@ GrB_Info GrB_Matrix_exportHint(GrB_Format *format, GrB_Matrix A);
     GrB_Info GrB_Matrix_apply_BinaryOp2nd_##T(GrB_Matrix C, const GrB_Matrix Mask,              \
                                               const GrB_BinaryOp accum, const GrB_BinaryOp op,  \
                                               const GrB_Matrix A, ctype y,                      \
-                                              const GrB_Descriptor desc);
+                                              const GrB_Descriptor desc);                       \
+    GrB_Info GrB_Matrix_select_##T(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, \
+                                   const GrB_IndexUnaryOp op, const GrB_Matrix A, ctype y,      \
+                                   const GrB_Descriptor desc);
 
 #define GB_DECLARE_TYPED_VECTOR(T, ctype)                                                          \
     GrB_Info GrB_Vector_build_##T(GrB_Vector w, const GrB_Index *I, const ctype *X,             \
@@ -224,7 +229,10 @@ GrB_Info GrB_Matrix_exportHint(GrB_Format *format, GrB_Matrix A);
     GrB_Info GrB_Vector_apply_BinaryOp2nd_##T(GrB_Vector w, const GrB_Vector mask,              \
                                               const GrB_BinaryOp accum, const GrB_BinaryOp op,  \
                                               const GrB_Vector u, ctype y,                      \
-                                              const GrB_Descriptor desc);
+                                              const GrB_Descriptor desc);                       \
+    GrB_Info GrB_Vector_select_##T(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, \
+                                   const GrB_IndexUnaryOp op, const GrB_Vector u, ctype y,      \
+                                   const GrB_Descriptor desc);
 
 #define GB_FOR_EACH_TYPE(X)                                                                        \
     X(BOOL, bool)                                                                                  \
@@ -298,6 +306,16 @@ GrB_Info GrB_Matrix_apply_BinaryOp2nd_Scalar(GrB_Matrix C, const GrB_Matrix Mask
                                              const GrB_BinaryOp accum, const GrB_BinaryOp op,
                                              const GrB_Matrix A, const GrB_Scalar y,
                                              const GrB_Descriptor desc);
+/* select (reference core/matrix.py:2452-2551, core/vector.py:1463-1560): C<M> = accum(C, the
+ * entries of A' that the index-unary operator keeps for thunk y).  Positional operators look at
+ * (i, j) of A' and cast y to INT64; GrB_VALUE*_T cast the entry and y to T for the comparison
+ * only: the kept entries carry A's own values.  An empty y is GrB_EMPTY_OBJECT. */
+GrB_Info GrB_Matrix_select_Scalar(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum,
+                                  const GrB_IndexUnaryOp op, const GrB_Matrix A, const GrB_Scalar y,
+                                  const GrB_Descriptor desc);
+GrB_Info GrB_Vector_select_Scalar(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum,
+                                  const GrB_IndexUnaryOp op, const GrB_Vector u, const GrB_Scalar y,
+                                  const GrB_Descriptor desc);
 
 /* ---------------------------------------------------------------- the hot path */
 /* C<Mask> = C accum (A' (+).(x) B')      replaces SuiteSparse GrB_mxm */

@@ -58,6 +58,13 @@ UNOPS = ["IDENTITY", "AINV", "MINV", "ABS", "LNOT", "ONE", "BNOT",
          "SIN", "COS", "TAN"]
 UCODE = {n: i for i, n in enumerate(UNOPS)}
 
+# index-unary (select) operators (reference core/operator/indexunary.py:98-114): the positional
+# ones are untyped, the VALUE* ones compare the entry with the thunk in the operator's type
+IDXOPS_POSITIONAL = ["TRIL", "TRIU", "DIAG", "OFFDIAG", "COLLE", "COLGT", "ROWLE", "ROWGT"]
+IDXOPS_VALUE = ["VALUEEQ", "VALUENE", "VALUEGT", "VALUEGE", "VALUELT", "VALUELE"]
+IDXOPS = IDXOPS_POSITIONAL + IDXOPS_VALUE
+ICODE = {n: i for i, n in enumerate(IDXOPS)}
+
 MONOIDS = ["PLUS", "TIMES", "MIN", "MAX", "ANY", "LOR", "LAND", "LXOR", "LXNOR",
            "BOR", "BAND", "BXOR", "BXNOR"]
 MCODE = {n: i for i, n in enumerate(MONOIDS)}
@@ -169,6 +176,15 @@ def unop_table():
     return out
 
 
+def idxop_table():
+    """-> list of (name, opcode name, type or None for positional)."""
+    out = [(f"GrB_{op}", op, None) for op in IDXOPS_POSITIONAL]
+    for op in IDXOPS_VALUE:
+        for t in TYPES:
+            out.append((f"GrB_{op}_{t[0]}", op, t[0]))
+    return out
+
+
 def monoid_table():
     """-> list of (name, monoid code name, type, binop name)."""
     out = []
@@ -248,6 +264,7 @@ HEADER_NOTE = "/* GENERATED by tools/gen_builtins.py -- do not edit. */\n"
 def main():
     binops = binop_table()
     unops = unop_table()
+    idxops = idxop_table()
     monoids = monoid_table()
     semirings = semiring_table(binops, monoids)
     bmap = {b[0]: b for b in binops}
@@ -266,6 +283,11 @@ def main():
     for i, n in enumerate(UNOPS):
         lines.append(f"    GBAMD_UOP_{n} = {i},\n")
     lines.append(f"    GBAMD_UOP_COUNT = {len(UNOPS)}\n}};\n")
+    lines.append("/* index-unary (select) operator codes: positional first, then value */\n"
+                 "enum gbamd_idxop_code {\n")
+    for i, n in enumerate(IDXOPS):
+        lines.append(f"    GBAMD_IOP_{n} = {i},\n")
+    lines.append(f"    GBAMD_IOP_COUNT = {len(IDXOPS)}\n}};\n")
     lines.append("/* monoid codes */\nenum gbamd_monoid_code {\n")
     for i, n in enumerate(MONOIDS):
         lines.append(f"    GBAMD_MON_{n} = {i},\n")
@@ -284,6 +306,9 @@ def main():
     d.append("/* builtin unary operators (reference core/operator/unary.py) */\n")
     for u in unops:
         d.append(f"GB_EXTERN GrB_UnaryOp {u[0]};\n")
+    d.append("/* builtin index-unary operators (reference core/operator/indexunary.py:98-114) */\n")
+    for u in idxops:
+        d.append(f"GB_EXTERN GrB_IndexUnaryOp {u[0]};\n")
     d.append("/* builtin monoids (reference core/operator/monoid.py:179-195) */\n")
     for m in monoids:
         d.append(f"GB_EXTERN GrB_Monoid {m[0]};\n")
@@ -308,6 +333,10 @@ def main():
         c.append(f"GB_BinaryOp_opaque B_{b[0]} = {{GB_MAGIC, GBAMD_OP_{b[1]}, {x}, {x}, &T_{b[3]}, \"{b[0]}\"}};\n")
     for u in unops:
         c.append(f"GB_UnaryOp_opaque U_{u[0]} = {{GB_MAGIC, GBAMD_UOP_{u[1]}, &T_{u[2]}, &T_{u[2]}, \"{u[0]}\"}};\n")
+    for u in idxops:
+        x = f"&T_{u[2]}" if u[2] else "nullptr"
+        y = f"&T_{u[2]}" if u[2] else "&T_INT64"
+        c.append(f"GB_IndexUnaryOp_opaque I_{u[0]} = {{GB_MAGIC, GBAMD_IOP_{u[1]}, {x}, {y}, \"{u[0]}\"}};\n")
     for m in monoids:
         c.append(f"GB_Monoid_opaque M_{m[0]} = {{GB_MAGIC, GBAMD_MON_{m[1]}, &T_{m[2]}, &B_{m[3]}, \"{m[0]}\"}};\n")
     for s in semirings:
@@ -324,6 +353,8 @@ def main():
         c.append(f"GrB_BinaryOp {b[0]} = &B_{b[0]};\n")
     for u in unops:
         c.append(f"GrB_UnaryOp {u[0]} = &U_{u[0]};\n")
+    for u in idxops:
+        c.append(f"GrB_IndexUnaryOp {u[0]} = &I_{u[0]};\n")
     for m in monoids:
         c.append(f"GrB_Monoid {m[0]} = &M_{m[0]};\n")
     for s in semirings:
@@ -349,6 +380,8 @@ def main():
         c.append(f"    {{\"{name}\", 4, (void*)&D_{name}}},\n")
     for u in unops:
         c.append(f"    {{\"{u[0]}\", 5, (void*)&U_{u[0]}}},\n")
+    for u in idxops:
+        c.append(f"    {{\"{u[0]}\", 6, (void*)&I_{u[0]}}},\n")
     c.append("    {nullptr, -1, nullptr}\n};\n")
     _write_if_changed(os.path.join(ROOT, "graph-python_amd", "csrc", "gb_builtins.cpp"), "".join(c))
 
@@ -359,11 +392,15 @@ def main():
     p.append("BINOP_CODES = " + repr(BINOPS) + "\n\n")
     p.append("MONOID_CODES = " + repr(MONOIDS) + "\n\n")
     p.append("UNOP_CODES = " + repr(UNOPS) + "\n\n")
+    p.append("IDXOP_CODES = " + repr(IDXOPS) + "\n\n")
     p.append("# name: (opcode name, xtype or None for positional, ztype)\nBINOPS = {\n")
     for b in binops:
         p.append(f"    {b[0]!r}: ({b[1]!r}, {b[2]!r}, {b[3]!r}),\n")
     p.append("}\n\n# name: (opcode name, type)\nUNOPS = {\n")
     for u in unops:
+        p.append(f"    {u[0]!r}: ({u[1]!r}, {u[2]!r}),\n")
+    p.append("}\n\n# name: (opcode name, type or None for positional)\nINDEXUNARYOPS = {\n")
+    for u in idxops:
         p.append(f"    {u[0]!r}: ({u[1]!r}, {u[2]!r}),\n")
     p.append("}\n\n# name: (monoid code name, type, binop name)\nMONOIDS = {\n")
     for m in monoids:
@@ -376,7 +413,7 @@ def main():
         p.append(f"    {k!r}: {v!r},\n")
     p.append("}\n")
     _write_if_changed(os.path.join(ROOT, "graph-python_amd", "graphblas_amd", "_builtins.py"), "".join(p))
-    print(f"types={len(TYPES)} binops={len(binops)} unops={len(unops)} monoids={len(monoids)} "
+    print(f"types={len(TYPES)} binops={len(binops)} unops={len(unops)} idxops={len(idxops)} monoids={len(monoids)} "
           f"semirings={len(semirings)} (+{sum(len(s[3]) for s in semirings)} aliases) "
           f"descriptors={len(DESCS)}")
 
