@@ -71,7 +71,8 @@ GB_HD D gb_cast(S x) {
 }
 
 // ------------------------------------------------------------------ ops
-GB_HD bool gb_op_is_positional(int op) { return op >= GBAMD_OP_FIRSTI; }
+// FIRSTI .. SECONDJ1 only: ATAN2 .. COPYSIGN have higher codes
+GB_HD bool gb_op_is_positional(int op) { return op >= GBAMD_OP_FIRSTI && op <= GBAMD_OP_SECONDJ1; }
 GB_HD bool gb_op_is_cmp(int op) { return op >= GBAMD_OP_EQ && op <= GBAMD_OP_LE; }
 
 GB_HD int gb_bool_rename(int op) {
@@ -100,6 +101,35 @@ GB_HD T gb_idiv(T x, T y) {
         if (y == 0) return x == 0 ? (T)0 : gb_tmax<T>();
         return (T)(x / y);
     }
+}
+
+// Integer x ** y: the saturating cast of the correctly rounded double pow(x, y), as SuiteSparse
+// defines it, computed without a libm pow (the device's is not exact where the result is an
+// integer: pow(3., 1.) may come out as 2.99.., which truncates to 2).  An exact magnitude below
+// 2^64 converts to the correctly rounded double; anything larger saturates in every integer type.
+template <class T>
+GB_HD T gb_ipow(T x, T y) {
+    bool xneg = false, yneg = false;
+    if constexpr (std::is_signed<T>::value) {
+        xneg = x < 0;
+        yneg = y < 0;
+    }
+    const uint64_t ax = xneg ? 0 - (uint64_t)(int64_t)x : (uint64_t)x;
+    const uint64_t ay = yneg ? 0 - (uint64_t)(int64_t)y : (uint64_t)y;
+    const bool neg = xneg && (ay & 1);
+    if (ay == 0) return (T)1;
+    if (ax == 0) return yneg ? gb_tmax<T>() : (T)0;  // pow(0, negative) is +inf
+    if (ax == 1) return neg ? (T)-1 : (T)1;
+    if (yneg) return (T)0;  // |x| >= 2: |x ** y| <= 1/2 truncates to 0
+    uint64_t m = 1;
+    bool over = ay >= 64;
+    for (uint64_t k = 0; !over && k < ay; k++) {
+        if (m > ~(uint64_t)0 / ax) over = true;
+        else m *= ax;
+    }
+    if (over) return neg ? gb_tmin<T>() : gb_tmax<T>();
+    const double r = (double)m;
+    return gb_cast<T, double>(neg ? -r : r);
 }
 
 template <class T>
@@ -194,7 +224,7 @@ GB_HD T gb_binop(int op, T x, T y) {
         case GBAMD_OP_POW:
             if constexpr (std::is_same<T, float>::value) return powf(x, y);
             else if constexpr (std::is_same<T, double>::value) return pow(x, y);
-            else return gb_cast<T, double>(pow((double)x, (double)y));
+            else return gb_ipow(x, y);
         case GBAMD_OP_ISEQ: return x == y ? one : zero;
         case GBAMD_OP_ISNE: return x != y ? one : zero;
         case GBAMD_OP_ISGT: return x > y ? one : zero;
@@ -250,7 +280,9 @@ GB_HD T gb_unop(int op, T x) {
     } else {
         switch (op) {
         case GBAMD_UOP_IDENTITY: return x;
-        case GBAMD_UOP_AINV: return gb_wrap_sub((T)0, x);
+        case GBAMD_UOP_AINV:
+            if constexpr (std::is_floating_point<T>::value) return -x;  // 0 - x would lose the sign of -(+0)
+            else return gb_wrap_sub((T)0, x);
         case GBAMD_UOP_MINV:
             if constexpr (gb_traits<T>::is_int) return gb_idiv((T)1, x);
             else return (T)1 / x;

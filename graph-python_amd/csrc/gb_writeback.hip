@@ -7,8 +7,13 @@
 // word-parallel (vectors) or entry-parallel (matrices) merge runs.
 //
 // Mixed-type accumulators (accum type != C type) are evaluated by casting C
-// and T into the accumulator type, merging there and casting back; entries
-// present only in C therefore make a round trip through the accumulator type.
+// and T into the accumulator type, merging there and casting back.  Entries
+// the merge takes from C unchanged (outside the mask, or under accum with no T
+// entry) are then rewritten from C's own values, so they keep their bits
+// (Z = accum(C, T) has C's type; a round trip INT64 -> FP64 -> INT64 would
+// turn 2^53 + 1 into 2^53).  Entries only T holds are likewise rewritten from
+// T cast straight to C's type, as SuiteSparse does: the accumulator's type
+// only matters where the accumulator runs.
 #include "gb_dispatch.cuh"
 #include "gb_internal.h"
 
@@ -155,7 +160,7 @@ __global__ __launch_bounds__(WB_BLOCK) void k_vec_merge(
     int64_t n, const uint64_t *__restrict__ cbits, const CT *__restrict__ cvals, bool c_iso,
     const uint64_t *__restrict__ tbits, const CT *__restrict__ tvals, bool t_iso, const uint64_t *__restrict__ mbits,
     bool mcomp, bool replace, int accum, uint64_t *__restrict__ obits, CT *__restrict__ ovals,
-    unsigned long long *__restrict__ count, unsigned long long *__restrict__ gst) {
+    uint64_t *__restrict__ kbits, unsigned long long *__restrict__ count, unsigned long long *__restrict__ gst) {
     unsigned long long mine = 0;
     // 64 consecutive elements per wave -> one output word per wave
     for (int64_t base = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) & ~63LL; base < n;
@@ -166,6 +171,7 @@ __global__ __launch_bounds__(WB_BLOCK) void k_vec_merge(
         bool t = inr && gb_bit(tbits, i);
         bool m = inr && (mbits ? (gb_bit(mbits, i) != mcomp) : !mcomp);
         bool have = false;
+        int from = 0;  // 1: C's entry unchanged, 2: T's entry unchanged
         CT v = CT();
         if (m) {
             if (accum >= 0 && c && t) {
@@ -174,22 +180,42 @@ __global__ __launch_bounds__(WB_BLOCK) void k_vec_merge(
             } else if (t) {
                 v = tvals[t_iso ? 0 : i];
                 have = true;
+                from = 2;
             } else if (accum >= 0 && c) {
                 v = cvals[c_iso ? 0 : i];
                 have = true;
+                from = 1;
             }
         } else if (!replace && c) {
             v = cvals[c_iso ? 0 : i];
             have = true;
+            from = 1;
         }
         if (have) ovals[i] = v;
         unsigned long long word = __ballot(have);
+        if (kbits) {  // uniform branch; two planes of (n + 63) / 64 words: from C, from T
+            unsigned long long kw = __ballot(from == 1), tw = __ballot(from == 2);
+            if ((threadIdx.x & 63) == 0) {
+                kbits[base >> 6] = kw;
+                kbits[((n + 63) >> 6) + (base >> 6)] = tw;
+            }
+        }
         if ((threadIdx.x & 63) == 0) {
             obits[base >> 6] = word;
             mine += __popcll(word);
         }
     }
     gb_grid_add((long long)mine, count, gst);
+}
+
+// ovals[i] = cvals[i] wherever kbits is set (the entries a mixed-type merge took unchanged)
+template <class CT>
+__global__ __launch_bounds__(WB_BLOCK) void k_vec_restore(int64_t n, const uint64_t *__restrict__ kbits,
+                                                          const CT *__restrict__ cvals, bool c_iso,
+                                                          CT *__restrict__ ovals) {
+    WB_STRIDE(i, n) {
+        if (gb_bit(kbits, i)) ovals[i] = cvals[c_iso ? 0 : i];
+    }
 }
 
 static void cast_vec_result(gb_vec_result &T, int code) {
@@ -242,17 +268,27 @@ bool gb_writeback_vector(GB_Obj *C, gb_vec_result &T, GB_Obj *M, const gb_desc &
     if (wcode != ct) {
         cvals = gb_bitmap_vals_as(cv, wcode, s);
     }
+    // T cast straight to C's type, for the entries only T holds
+    const void *t_direct = nullptr;
+    if (wcode != ct && T.tcode != wcode && n) {
+        int64_t nv = T.iso ? 1 : n;
+        void *td = s.get<char>(nv * gb_type_size(ct));
+        gb_cast_array(td, ct, T.dense, T.tcode, nv);
+        t_direct = td;
+    }
+    const bool t_iso = T.iso;
     cast_vec_result(T, wcode);
     uint64_t *obits = gb_malloc_n<uint64_t>(gb_words(n));
     void *ovals = gb_malloc(n * gb_type_size(wcode));
     int64_t *cnt = gb_malloc_n<int64_t>(1);
     gb_memset(cnt, 0, sizeof(int64_t));
+    uint64_t *kbits = (wcode != ct && n) ? s.get<uint64_t>(2 * gb_words(n)) : nullptr;
     if (n) {
         gb_with_type(wcode, [&](auto z) {
             using W = decltype(z);
             hipLaunchKernelGGL(k_vec_merge<W>, dim3(wb_grid(n, 1024)), dim3(WB_BLOCK), 0, gb_stream(), n, cv.bits,
                                (const W *)cvals, c_iso, T.bits, (const W *)T.dense, T.iso, mask.bits, mask.comp,
-                               d.replace, accum ? accum->opcode : -1, obits, (W *)ovals,
+                               d.replace, accum ? accum->opcode : -1, obits, (W *)ovals, kbits,
                                (unsigned long long *)cnt, gb_device_state());
         });
         GB_LAUNCH_CHECK();
@@ -263,6 +299,17 @@ bool gb_writeback_vector(GB_Obj *C, gb_vec_result &T, GB_Obj *M, const gb_desc &
         gb_cast_array(o2, ct, ovals, wcode, n);
         gb_free(ovals);
         ovals = o2;
+        if (n) {
+            gb_with_type(ct, [&](auto z) {
+                using CT = decltype(z);
+                hipLaunchKernelGGL(k_vec_restore<CT>, dim3(wb_grid(n, 1024)), dim3(WB_BLOCK), 0, gb_stream(), n, kbits,
+                                   (const CT *)cv.vals, cv.iso, (CT *)ovals);
+                if (t_direct)
+                    hipLaunchKernelGGL(k_vec_restore<CT>, dim3(wb_grid(n, 1024)), dim3(WB_BLOCK), 0, gb_stream(), n,
+                                       kbits + gb_words(n), (const CT *)t_direct, t_iso, (CT *)ovals);
+            });
+            GB_LAUNCH_CHECK();
+        }
     }
     gb_install_bitmap(C, n, obits, ovals, false, cnt);
     return false;
@@ -378,8 +425,10 @@ __global__ __launch_bounds__(WB_BLOCK) void k_merge_place_t(
         const int32_t j = tci[e];
         const int64_t a = crp[r], b = crp[r + 1];
         const int64_t p = wb_lower_bound(cci, a, b, j);
+        const bool hit = p < b && cci[p] == j;
+        if (accum == -2 && hit) continue;  // restore pass: only the entries C does not hold
         CT v = tvx[t_iso ? 0 : e];
-        if (accum >= 0 && p < b && cci[p] == j) v = gb_binop<CT>(accum, cvx[c_iso ? 0 : p], v);
+        if (accum >= 0 && hit) v = gb_binop<CT>(accum, cvx[c_iso ? 0 : p], v);
         const int64_t o = st[e] + sc[p];
         oci[o] = j;
         ovx[o] = v;
@@ -426,6 +475,14 @@ void gb_writeback_matrix(GB_Obj *C, gb_mat_result &T, GB_Obj *M, const gb_desc &
     gb_get_csr(cv, C);
     gb_scratch s;
     const void *cvals = (wcode != ct) ? gb_view_vals_as(cv, wcode, s) : cv.vals;
+    // T cast straight to C's type, for the entries only T holds
+    const void *t_direct = nullptr;
+    if (wcode != ct && T.tcode != wcode && T.nvals) {
+        int64_t nv = T.iso ? 1 : T.nvals;
+        void *td = s.get<char>(nv * gb_type_size(ct));
+        gb_cast_array(td, ct, T.vals, T.tcode, nv);
+        t_direct = td;
+    }
     cast_mat_result(T, wcode);
     const bool has_mask = mask.present;
     const int64_t cnz = cv.nvals, tnz = T.nvals;
@@ -464,17 +521,31 @@ void gb_writeback_matrix(GB_Obj *C, gb_mat_result &T, GB_Obj *M, const gb_desc &
                                cv.iso, accum ? accum->opcode : -1, sc, st, oci, (W *)ovx);
     });
     GB_LAUNCH_CHECK();
+    if (wcode != ct) {
+        void *o2 = gb_malloc(std::max<int64_t>(nz, 1) * gb_type_size(ct));
+        gb_cast_array(o2, ct, ovx, wcode, nz);
+        gb_free(ovx);
+        ovx = o2;
+        // the entries kept from C, and those only T holds: place them again, from C's own
+        // values and from T cast straight to C's type
+        gb_with_type(ct, [&](auto z) {
+            using CT = decltype(z);
+            if (cnz)
+                hipLaunchKernelGGL((k_merge_place_c<CT>), dim3(wb_grid(cnz)), dim3(WB_BLOCK), 0, gb_stream(), nrows,
+                                   cnz, cv.rowptr, cv.colidx, (const CT *)cv.vals, cv.iso, T.rowptr, T.colidx, sc, st,
+                                   oci, (CT *)ovx);
+            if (tnz && t_direct)
+                hipLaunchKernelGGL((k_merge_place_t<CT>), dim3(wb_grid(tnz)), dim3(WB_BLOCK), 0, gb_stream(), nrows,
+                                   tnz, T.rowptr, T.colidx, (const CT *)t_direct, T.iso, cv.rowptr, cv.colidx,
+                                   (const CT *)cv.vals, cv.iso, -2, sc, st, oci, (CT *)ovx);
+        });
+        GB_LAUNCH_CHECK();
+    }
     gb_free(T.rowptr);
     gb_free(T.colidx);
     gb_free(T.vals);
     T.rowptr = nullptr;
     T.colidx = nullptr;
     T.vals = nullptr;
-    if (wcode != ct) {
-        void *o2 = gb_malloc(nz * gb_type_size(ct));
-        gb_cast_array(o2, ct, ovx, wcode, nz);
-        gb_free(ovx);
-        ovx = o2;
-    }
     gb_install_csr(C, nrows, ncols, nz, orp, oci, ovx, false);
 }

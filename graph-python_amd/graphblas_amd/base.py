@@ -450,7 +450,9 @@ class BaseType:
             if type(expr).__name__ == "TransposedMatrix" and type(self).__name__ == "Matrix":
                 from .matrix import MatrixExpression
 
-                expr = MatrixExpression("transpose", "GrB_transpose", [expr._matrix], at=True,
+                # C << A.T is GrB_transpose(C, ..., A) with no INP0 flag (reference core/base.py:381-391);
+                # with INP0 = TRAN the call would transpose A.T, i.e. copy A
+                expr = MatrixExpression("transpose", "GrB_transpose", [expr._matrix],
                                         dtype=expr.dtype, nrows=expr.nrows, ncols=expr.ncols)
             elif self._is_scalar:
                 if accum is not None:

@@ -55,8 +55,9 @@ def mmread(source, engine="auto", *, dup_op=None, name=None, **kwargs):
             if engine == "native":
                 raise
         else:
-            vals = True if dt == "BOOL" else v  # pattern: iso true, as from_coo with a scalar
-            return Matrix.from_coo(r, c, vals, dtype=dt, nrows=nr, ncols=nc, dup_op=dup_op, name=name)
+            if dt == "BOOL":  # pattern: iso true, as from_coo with a scalar (which takes no dup_op)
+                return Matrix.from_coo(r, c, True, dtype=dt, nrows=nr, ncols=nc, name=name)
+            return Matrix.from_coo(r, c, v, dtype=dt, nrows=nr, ncols=nc, dup_op=dup_op, name=name)
     from scipy.io import mmread as sp_mmread
 
     array = sp_mmread(source, **kwargs)

@@ -123,6 +123,9 @@ class Matrix(BaseType):
         if ncols is None:
             ncols = int(columns.max()) + 1 if columns.size else 0
         if np.ndim(values) == 0 and not isinstance(values, np.ndarray):
+            if dup_op is not None:  # reference core/matrix.py:947-951
+                raise ValueError("dup_op must be None if values is a scalar so that all "
+                                 "values can be identical.  Duplicate indices will be ignored.")
             dt = _values_dtype(values, dtype)
             C = cls(dt, nrows, ncols, name=name)
             n = rows.size

@@ -74,6 +74,9 @@ class Vector(BaseType):
         if size is None:
             size = int(indices.max()) + 1 if indices.size else 0
         if np.ndim(values) == 0 and not isinstance(values, np.ndarray):
+            if dup_op is not None:  # reference core/vector.py:773-777
+                raise ValueError("dup_op must be None if values is a scalar so that all "
+                                 "values can be identical.  Duplicate indices will be ignored.")
             dt = _values_dtype(values, dtype)
             v = cls(dt, size, name=name)
             if indices.size:

@@ -1,0 +1,251 @@
+"""Hand-worked checks of tests/dense_model.py, the numpy reference the GPU tests of the general
+operations (test_general_ops_gpu.py) compare with.  Not marked gpu: a wrong model must not be able
+to agree quietly with a wrong kernel.
+
+The golden file records no eWise, apply, reduce or transpose case of the reference; its accum and
+mask cases (C = A.dup(); C(mask, accum) << A.mxm(A) and the vxm ones) do exercise the write-back
+rule, with T the recorded unmasked product, so the model's write_back runs on those.
+"""
+import math
+
+import numpy as np
+
+import dense_model as dm
+
+
+def _b(name, dtype, x, y):
+    return dm.binop(name, dtype, np.array([x], dm.NP[dtype]), np.array([y], dm.NP[dtype]))[0]
+
+
+def _u(name, dtype, x):
+    return dm.unop(name, dtype, np.array([x], dm.NP[dtype]))[0]
+
+
+def _c(x, src, dst):
+    return dm.cast(np.array([x], dm.NP[src]), dst)[0]
+
+
+def test_dense_model_rules():
+    # integer division
+    assert _b("div", "INT8", -128, -1) == -128
+    assert _b("div", "INT8", 5, 0) == 127
+    assert _b("div", "INT8", -5, 0) == -128
+    assert _b("div", "UINT8", 0, 0) == 0
+    assert _b("div", "UINT8", 7, 0) == 255
+    assert _b("div", "INT8", 0, 0) == 0
+    assert _b("div", "INT32", -7, 2) == -3 and _b("div", "INT32", 7, -2) == -3  # toward zero
+    assert _b("div", "INT32", -7, -2) == 3 and _b("div", "INT32", -6, 2) == -3
+    assert _b("div", "INT64", -2**63, -1) == -2**63 and _b("div", "INT64", 5, -1) == -5
+    assert _b("rdiv", "INT8", 0, 5) == 127 and _b("rdiv", "INT16", 4, -9) == -2
+    assert _u("minv", "INT8", 0) == 127 and _u("minv", "INT8", -1) == -1 and _u("minv", "INT8", 2) == 0
+    assert _u("minv", "UINT16", 0) == 65535 and _u("minv", "UINT16", 1) == 1
+    # integer pow: the saturating cast of a float64 pow
+    assert _b("pow", "INT8", 3, 5) == 127 and _b("times", "INT8", _b("times", "INT8", 81, 3), 1) == -13
+    assert _b("pow", "INT64", -2, 63) == -2**63
+    assert _b("pow", "INT64", 2, 63) == 2**63 - 1
+    assert _b("pow", "INT32", 0, -1) == 2**31 - 1
+    assert _b("pow", "INT32", 2, -1) == 0
+    assert _b("pow", "UINT8", 2, 7) == 128 and _b("pow", "UINT8", 2, 8) == 255
+    assert _b("pow", "INT16", -3, 3) == -27 and _b("pow", "INT16", -9, 5) == -32768
+    # wrapping arithmetic
+    assert _b("plus", "INT8", 127, 1) == -128 and _b("minus", "UINT8", 0, 1) == 255
+    assert _b("rminus", "INT8", 1, -128) == 127 and _b("times", "UINT16", 256, 256) == 0
+    assert _b("times", "INT64", 2**62, 2) == -2**63
+    assert _u("ainv", "INT8", -128) == -128 and _u("abs", "INT8", -128) == -128 and _u("ainv", "UINT8", 1) == 255
+    # casts
+    assert _c(-1.5, "FP64", "UINT8") == 0
+    assert _c(300.7, "FP64", "INT8") == 127
+    assert _c(math.nan, "FP64", "INT32") == 0
+    assert _c(-5, "INT32", "INT64") == -5
+    assert _c(-5, "INT32", "UINT64") == 2**64 - 5
+    assert _c(-300.7, "FP32", "INT8") == -128 and _c(-1.9, "FP64", "INT8") == -1 and _c(2.9, "FP32", "UINT8") == 2
+    assert _c(math.inf, "FP64", "INT64") == 2**63 - 1 and _c(-math.inf, "FP64", "INT64") == -2**63
+    assert _c(2.0**63, "FP64", "INT64") == 2**63 - 1 and _c(2.0**64, "FP64", "UINT64") == 2**64 - 1
+    assert _c(300, "INT32", "UINT8") == 44 and _c(200, "UINT8", "INT8") == -56
+    assert _c(2**53 + 1, "INT64", "FP64") == 2.0**53
+    assert _c(0.25, "FP64", "BOOL") and _c(math.nan, "FP64", "BOOL") and not _c(-0.0, "FP64", "BOOL")
+    assert _c(True, "BOOL", "INT8") == 1 and _c(True, "BOOL", "FP32") == 1.0
+    # round is half away from zero
+    assert _u("round", "FP64", 2.5) == 3.0
+    r = _u("round", "FP64", -0.5)
+    assert r == -1.0
+    assert _u("round", "FP32", 0.5) == 1.0 and _u("round", "FP64", 1.5) == 2.0 and _u("round", "FP64", -2.5) == -3.0
+    assert _u("round", "FP64", 0.49999999999999994) == 0.0
+    z = _u("round", "FP64", -0.25)
+    assert z == 0.0 and np.signbit(z)
+    assert np.isnan(_u("round", "FP64", math.nan)) and _u("round", "FP64", -math.inf) == -math.inf
+    # ainv of a float is -x: the sign of zero flips
+    assert np.signbit(_u("ainv", "FP64", 0.0)) and not np.signbit(_u("ainv", "FP32", -0.0))
+    # float min / max omit NaN
+    assert _b("min", "FP64", math.nan, 2.0) == 2.0 and _b("max", "FP32", 1.0, math.nan) == 1.0
+    assert np.isnan(_b("min", "FP64", math.nan, math.nan))
+    # IEEE remainder and C fmod
+    assert _b("remainder", "FP64", 5.0, 3.0) == -1.0 and _b("fmod", "FP64", 5.0, 3.0) == 2.0
+    assert _b("remainder", "FP64", 7.0, 2.0) == -1.0 and _b("fmod", "FP64", -7.0, 2.0) == -1.0  # ties to even
+    assert np.isnan(_b("remainder", "FP64", 1.0, 0.0)) and np.isnan(_b("fmod", "FP32", math.inf, 2.0))
+    assert _b("ldexp", "FP32", 3.0, -2.0) == 0.75 and _b("copysign", "FP64", 2.0, -0.0) == -2.0
+    # bool renames
+    T, F = True, False
+    for x in (F, T):
+        for y in (F, T):
+            assert _b("plus", "BOOL", x, y) == _b("max", "BOOL", x, y) == (x or y)
+            assert _b("times", "BOOL", x, y) == _b("min", "BOOL", x, y) == (x and y)
+            assert _b("minus", "BOOL", x, y) == _b("ne", "BOOL", x, y) == _b("rminus", "BOOL", x, y) == (x != y)
+            assert _b("div", "BOOL", x, y) == x and _b("rdiv", "BOOL", x, y) == y
+            assert _b("pow", "BOOL", x, y) == (x or not y)
+            assert _b("eq", "BOOL", x, y) == _b("iseq", "BOOL", x, y) == _b("lxnor", "BOOL", x, y) == (x == y)
+            assert _b("gt", "BOOL", x, y) == _b("isgt", "BOOL", x, y) == (x and not y)
+            assert _b("le", "BOOL", x, y) == (not x or y) and _b("pair", "BOOL", x, y)
+        assert _u("minv", "BOOL", x) and _u("lnot", "BOOL", x) == (not x) and _u("ainv", "BOOL", x) == x
+    # logical and is* operators on other types return 1/0 of that type; comparisons return bool
+    assert _b("lor", "INT8", 0, -3) == 1 and _b("lor", "INT8", 0, -3).dtype == np.int8
+    assert _b("land", "FP32", 0.5, math.nan) == 1.0 and _b("lxor", "UINT8", 2, 3) == 0
+    assert _b("lxnor", "FP64", 0.0, -0.0) == 1.0 and _u("lnot", "FP64", -0.0) == 1.0 and _u("lnot", "INT16", 7) == 0
+    assert _b("isgt", "INT8", 3, 2) == 1 and _b("isgt", "INT8", 3, 2).dtype == np.int8
+    assert _b("isne", "FP64", math.nan, math.nan) == 1.0 and _b("iseq", "FP32", 1.0, 1.0).dtype == np.float32
+    assert _b("gt", "UINT64", 2**64 - 1, 2**63) and _b("gt", "UINT64", 1, 0).dtype == np.bool_
+    assert not _b("eq", "FP64", math.nan, math.nan) and _b("ne", "FP64", math.nan, math.nan)
+    # bitwise
+    assert _b("bxnor", "UINT8", 0b1100, 0b1010) == 0b11111001 and _b("bxnor", "INT8", 5, 5) == -1
+    assert _u("bnot", "UINT16", 1) == 65534 and _u("bnot", "INT8", 0) == -1
+    assert _b("any", "INT8", 3, 4) == 4 and _b("first", "INT8", 3, 4) == 3 and _b("pair", "FP32", 3, 4) == 1.0
+
+
+def test_monoid_folds_match_their_definition():
+    rng = np.random.default_rng(5)
+    for name, dtypes in [("plus", ["INT8", "UINT64"]), ("times", ["INT8", "UINT16"]), ("min", ["INT16", "FP32"]),
+                         ("max", ["UINT8", "FP64"]), ("lor", ["BOOL"]), ("land", ["BOOL"]), ("lxor", ["BOOL"]),
+                         ("lxnor", ["BOOL"]), ("bor", ["UINT8"]), ("band", ["UINT32"]), ("bxor", ["UINT64"]),
+                         ("bxnor", ["UINT8", "UINT64"])]:
+        for dt in dtypes:
+            for n in (1, 2, 3, 8, 9):
+                if dt == "BOOL":
+                    for bias in (0.1, 0.5, 0.9, 1.0):
+                        v = rng.random(n) < bias
+                        assert dm.monoid_fold(name, dt, v) == dm.monoid_fold_sequential(name, dt, v), (name, n)
+                    continue
+                v = rng.integers(0, 200, n).astype(dm.NP[dt])
+                if dm.is_float(dt):
+                    v[0] = np.nan
+                a, b = dm.monoid_fold(name, dt, v), dm.monoid_fold_sequential(name, dt, v)
+                assert np.array_equal(a, b, equal_nan=dm.is_float(dt)) and np.asarray(a).dtype == dm.NP[dt], (name, dt, n)
+    assert dm.monoid_identity("min", "INT8") == 127 and dm.monoid_identity("max", "UINT8") == 0
+    assert dm.monoid_identity("min", "FP32") == np.inf and dm.monoid_identity("band", "UINT16") == 65535
+    assert dm.monoid_identity("times", "FP64") == 1.0 and dm.monoid_identity("lxnor", "BOOL")
+    # the identity does not change a fold
+    for name, dt in [("plus", "INT8"), ("times", "UINT8"), ("min", "INT32"), ("max", "FP64"), ("lor", "BOOL"),
+                     ("land", "BOOL"), ("lxor", "BOOL"), ("lxnor", "BOOL"), ("bor", "UINT8"), ("band", "UINT8"),
+                     ("bxor", "UINT8"), ("bxnor", "UINT8")]:
+        for x in ([0, 1, 5, 77] if dt != "BOOL" else [False, True]):
+            x = np.array([x], dm.NP[dt])
+            assert dm.binop(name, dt, x, np.array([dm.monoid_identity(name, dt)]))[0] == x[0], (name, dt)
+
+
+def test_ewise_apply_reduce_transpose_small():
+    A = dm.to_dense((2, 3), ([0, 0, 1], [0, 2, 1]), np.array([1, -2, 3], np.int8))
+    B = dm.to_dense((2, 3), ([0, 1, 1], [2, 1, 2]), np.array([2.5, 300.0, -1.0]))
+    p, v = dm.ewise("mult", "plus", "FP64", A, B)
+    assert dm.to_coo((p, v))[0].tolist() == [0, 1] and v[p].tolist() == [0.5, 303.0]
+    p, v = dm.ewise("add", "gt", "FP64", A, B)  # one-sided entries: the value cast to bool
+    assert v.dtype == np.bool_ and p.sum() == 4
+    assert v[0, 0] and not v[0, 2] and not v[1, 1] and v[1, 2]
+    p, v = dm.ewise("add", "plus", "INT8", A, B)  # operands cast first: 300.0 -> 127, 3 + 127 wraps
+    assert v.dtype == np.int8 and v[1, 1] == -126 and v[0, 2] == 0 and v[1, 2] == -1 and v[0, 0] == 1
+    p, v = dm.apply("minus", "INT8", A, right=np.int64(130))  # the scalar is cast to the operator's type
+    assert v[0, 0] == 127 and v[0, 2] == 124
+    p, v = dm.apply("minus", "INT8", A, left=np.int8(1))
+    assert v[0, 2] == 3 and v[1, 1] == -2 and not p[1, 0]
+    assert dm.reduce_scalar("plus", "INT8", A) == 2 and dm.reduce_scalar("plus", "INT8", (A[0] & False, A[1])) is None
+    p, v = dm.reduce_rows("min", "INT8", A)
+    assert p.tolist() == [True, True] and v.tolist() == [-2, 3]
+    p, v = dm.reduce_cols("max", "FP64", B)
+    assert p.tolist() == [False, True, True] and v[1:].tolist() == [300.0, 2.5]
+    tp, tv = dm.transpose(A)
+    assert tp.shape == (3, 2) and tv[2, 0] == -2 and tp[1, 1] and not tp[0, 1]
+
+
+def test_build_folds_in_input_order():
+    idx = np.array([2, 0, 2, 2, 0, 1])
+    vals = np.array([10, 1, 3, 4, 7, 9])
+    for op, want in [("plus", [8, 9, 17]), ("minus", [-6, 9, 3]), ("first", [1, 9, 10]), ("second", [7, 9, 4]),
+                     ("min", [1, 9, 3]), ("rminus", [6, 9, 11])]:
+        p, v = dm.build((4,), (idx,), vals, op, "INT64")
+        assert p.tolist() == [True, True, True, False] and v[:3].tolist() == want, op
+    # the cast runs before the fold: 200 + 100 as INT8 is -56 + 100
+    p, v = dm.build((1, 2), ([0, 0], [1, 1]), np.array([200, 100]), "plus", "INT8")
+    assert v[0, 1] == 44 and p.sum() == 1
+    p, v = dm.build((2,), ([1, 1, 1],), np.array([0.5, 2.0, 0.0]), "plus", "BOOL")  # lor of the casts
+    assert v[1] and v.dtype == np.bool_
+
+
+def test_write_back_rules():
+    big = 2**53 + 1
+    C = dm.to_dense((5,), ([0, 1, 2, 3],), np.array([big, -(2**62) - 3, 7, 8], np.int64))
+    T = dm.to_dense((5,), ([1, 2, 4],), np.array([0.5, 1.75, 300.25]))
+    # plus evaluated in FP64: untouched entries keep their bits, both -> cast(float(c) + t)
+    p, v = dm.write_back(C, T, accum="plus", accum_dtype="FP64")
+    assert p.all() and v.tolist() == [big, -(2**62), 8, 8, 300]
+    # in INT64 (the default for an untyped accumulator): t is cast first
+    p, v = dm.write_back(C, T, accum="plus")
+    assert v.tolist() == [big, -(2**62) - 3, 8, 8, 300]
+    M = dm.to_dense((5,), ([0, 2, 4],), np.array([False, True, True]))
+    p, v = dm.write_back(C, T, mask=M, mask_struct=True, accum="plus", accum_dtype="FP64")
+    assert p.all() and v.tolist() == [big, -(2**62) - 3, 8, 8, 300]
+    p, v = dm.write_back(C, T, mask=M, accum="plus", accum_dtype="FP64")  # value mask: index 0 is outside
+    assert v.tolist() == [big, -(2**62) - 3, 8, 8, 300]
+    p, v = dm.write_back(C, T, mask=M, mask_struct=True, mask_comp=True, replace=True)  # no accum: Z = T
+    assert p.tolist() == [False, True, False, False, False] and v[1] == 0
+    p, v = dm.write_back(C, T, mask=M, mask_struct=True, mask_comp=True, replace=True, accum="plus",
+                         accum_dtype="FP64")
+    assert p.tolist() == [False, True, False, True, False] and v[1] == -(2**62) and v[3] == 8
+    # no mask, no accum: C = T cast to C's type, old entries gone
+    p, v = dm.write_back(C, T)
+    assert p.tolist() == [False, True, True, False, True] and v[[1, 2, 4]].tolist() == [0, 1, 300]
+    # C UINT8 with max evaluated in INT64: the result wraps into UINT8; a T-only entry saturates
+    C8 = dm.to_dense((3,), ([0, 1],), np.array([200, 5], np.uint8))
+    T8 = dm.to_dense((3,), ([0, 1, 2],), np.array([300.0, -4.0, 1e9]))
+    p, v = dm.write_back(C8, T8, accum="max", accum_dtype="INT64")
+    assert v.tolist() == [44, 5, 255]
+
+
+def _gold(case, shape):
+    if "indices" in case:
+        return dm.to_dense(shape, (case["indices"],), np.array(case["values"]))
+    return dm.to_dense(shape, (case["rows"], case["cols"]), np.array(case["values"]))
+
+
+def _same(got, want):
+    return np.array_equal(got[0], want[0]) and np.array_equal(got[1][got[0]], want[1][want[0]])
+
+
+def test_write_back_on_the_reference_golden_cases(golden):
+    c = golden["cases"]
+    A = _gold(golden["A"], (7, 7))
+    v = _gold(golden["v"], (7,))
+    T = _gold(c["test_mxm"]["expected"], (7, 7))
+    assert _same(dm.write_back(A, T, accum="plus"), _gold(c["test_mxm_accum"]["expected"], (7, 7)))
+    mm = c["test_mxm_mask"]
+    vm, sm = _gold(mm["val_mask"], (7, 7)), _gold(mm["struct_mask"], (7, 7))
+    assert _same(dm.write_back(A, T, mask=vm), _gold(mm["expected_value"], (7, 7)))
+    assert _same(dm.write_back(A, T, mask=vm, mask_comp=True), _gold(mm["expected_comp"], (7, 7)))
+    assert _same(dm.write_back(A, T, mask=sm, mask_struct=True, replace=True),
+                 _gold(mm["expected_struct_replace"], (7, 7)))
+    t = _gold(c["test_vxm"]["expected"], (7,))
+    assert _same(dm.write_back(v, t, accum="plus"), _gold(c["test_vxm_accum"]["expected"], (7,)))
+    vmk = c["test_vxm_mask"]
+    vm, sm = _gold(vmk["val_mask"], (7,)), _gold(vmk["struct_mask"], (7,))
+    assert _same(dm.write_back(v, t, mask=sm, mask_struct=True), _gold(vmk["expected_struct"], (7,)))
+    assert _same(dm.write_back(v, t, mask=sm, mask_struct=True, mask_comp=True), _gold(vmk["expected_comp"], (7,)))
+    assert _same(dm.write_back(v, t, mask=vm, replace=True), _gold(vmk["expected_value_replace"], (7,)))
+
+
+def test_ulp_distance():
+    a = np.array([1.0, -1.0, 0.0, np.inf, np.nan], np.float32)
+    assert dm.ulp_distance(a, a) == 0
+    b = a.copy()
+    b[0] = np.nextafter(np.float32(1.0), np.float32(2.0))
+    b[1] = np.nextafter(np.nextafter(np.float32(-1.0), np.float32(-2.0)), np.float32(-2.0))
+    assert dm.ulp_distance(b, a) == 2
+    assert dm.ulp_distance(np.array([-0.0]), np.array([5e-324])) == 1
+    assert dm.ulp_distance(np.array([np.nan, 1.0]), np.array([1.0, 1.0])) == math.inf
+    assert dm.ulp_distance(np.array([np.inf]), np.array([-np.inf])) == math.inf
