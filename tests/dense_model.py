@@ -425,3 +425,194 @@ def ulp_distance(got, ref):
 
     g, r = key(got[~special]), key(ref[~special])
     return int(np.max(np.abs(g - r))) if g.size else 0
+
+
+# ---------------------------------------------------------------------- mxm, mxv, vxm
+POSITIONAL = {"firsti": ("i", 0), "firsti1": ("i", 1), "firstj": ("k", 0), "firstj1": ("k", 1),
+              "secondi": ("k", 0), "secondi1": ("k", 1), "secondj": ("j", 0), "secondj1": ("j", 1)}
+
+
+class Products:
+    """Every product of T = A (+).(x) B, grouped by output entry.  Entry e is T(rows[e], cols[e]);
+    its products are z[start[e]:end[e]] with the inner indices k[start[e]:end[e]] ascending."""
+
+    def __init__(self, shape, dtype, rows, cols, start, end, z, k, clash=None):
+        self.shape, self.dtype = shape, dtype
+        self.rows, self.cols, self.start, self.end, self.z, self.k = rows, cols, start, end, z, k
+        # per product: a float min / max multiplier met +0.0 and -0.0, and may return either
+        self.clash = np.zeros(z.size, bool) if clash is None else clash
+
+    @property
+    def segment(self):
+        """the entry number of every product"""
+        return np.repeat(np.arange(self.rows.size), self.end - self.start)
+
+    def lists(self):
+        """{(i, j): the products of that entry in ascending k}"""
+        return {(int(i), int(j)): self.z[s:e] for i, j, s, e in zip(self.rows, self.cols, self.start, self.end)}
+
+    def reordered(self, order):
+        """the products with every list reversed ("descending") or shuffled (a numpy Generator)"""
+        seg = self.segment
+        if isinstance(order, str):
+            assert order == "descending"
+            key = -np.arange(seg.size)
+        else:
+            key = order.permutation(seg.size)
+        return self.z[np.lexsort((key, seg))]
+
+    def fold(self, monoid, z=None):
+        """every list folded left to right, one call of the monoid's binary operator per product
+        (monoid_fold_sequential, run on all the lists at once)"""
+        z = self.z if z is None else z
+        acc = z[self.start].copy()
+        live = np.flatnonzero(self.end - self.start > 1)
+        t = 1
+        while live.size:
+            acc[live] = binop(monoid, self.dtype, acc[live], z[self.start[live] + t])
+            t += 1
+            live = live[self.end[live] - self.start[live] > t]
+        return acc
+
+    def dense(self, per_entry, fill=0):
+        """a per-entry array scattered to the shape of T"""
+        per_entry = np.asarray(per_entry)
+        out = np.full(self.shape, fill, per_entry.dtype)
+        out[self.rows, self.cols] = per_entry
+        return out
+
+    def member(self, rows, cols, values):
+        """for each (rows[q], cols[q]), an entry asked about once: is values[q] one of that entry's
+        products, compared by bits"""
+        lookup = self.dense(np.arange(self.rows.size), -1)
+        e = lookup[rows, cols]
+        assert (e >= 0).all()
+        want = np.full(self.rows.size, 0, self.z.dtype)
+        want[e] = values
+        u = np.dtype(f"u{self.z.dtype.itemsize}")
+        asked = want[self.segment]
+        hit = self.z.view(u) == asked.view(u)
+        if self.z.dtype.kind == "f":  # any NaN is the NaN; a clash product is a zero of either sign
+            hit |= (np.isnan(self.z) & np.isnan(asked)) | (self.clash & (self.z == asked))
+        ok = np.logical_or.reduceat(hit, self.start) if hit.size else np.zeros(0, bool)
+        return ok[e]
+
+
+def mxm_products(mul, dtype, A, B, tran0=False, tran1=False):
+    """The products of A (x) B.  `dtype` is the multiplier's input type: both operands are cast to
+    it first and z has binop_return_dtype(mul, dtype) (BOOL for the comparators).  A positional
+    multiplier ignores the values and `dtype` is its result type; the indices are those of the
+    operands as multiplied, after any transpose: A(i,k) . B(k,j) gives FIRSTI = i, FIRSTJ =
+    SECONDI = k, SECONDJ = j, and the `1` forms one more (the GxB positional operators; the same
+    reading as oracle/gb_oracle.c binop())."""
+    if tran0:
+        A = transpose(A)
+    if tran1:
+        B = transpose(B)
+    (ap, av), (bp, bv) = A, B
+    assert ap.shape[1] == bp.shape[0]
+    clash = None
+    n, m = ap.shape[0], bp.shape[1]
+    ai, ak = np.nonzero(ap)  # row-major: ascending k within a row
+    brow = bp.sum(axis=1)
+    bptr = np.r_[0, np.cumsum(brow)]
+    bj = np.nonzero(bp)[1]
+    cnt = brow[ak]
+    total = int(cnt.sum())
+    src = np.repeat(np.arange(ai.size), cnt)
+    within = np.arange(total) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    I, K = ai[src], ak[src]
+    J = bj[bptr[K] + within] if total else np.zeros(0, np.int64)
+    if mul in POSITIONAL:
+        which, plus = POSITIONAL[mul]
+        with np.errstate(over="ignore"):
+            z = ({"i": I, "k": K, "j": J}[which] + plus).astype(NP[dtype])
+        zt = dtype
+    else:
+        zt = binop_return_dtype(mul, dtype)
+        ax, bx = cast(av, dtype), cast(bv, dtype)
+        x, y = ax[I, K], bx[K, J]
+        z = cast(binop(mul, dtype, x, y), zt)
+        if mul in ("min", "max") and is_float(dtype):
+            clash = (x == 0) & (y == 0) & (np.signbit(x) != np.signbit(y))
+    order = np.argsort(I * m + J, kind="stable")  # keeps k ascending inside an entry
+    I, J, K, z = I[order], J[order], K[order], z[order]
+    clash = None if clash is None else clash[order]
+    key = I * m + J
+    start = np.flatnonzero(np.r_[True, key[1:] != key[:-1]]) if total else np.zeros(0, np.int64)
+    end = np.r_[start[1:], total] if total else np.zeros(0, np.int64)
+    return Products((n, m), zt, I[start], J[start], start, end, z, K, clash)
+
+
+def mxm(monoid, mul, dtype, A, B, tran0=False, tran1=False, products=False):
+    """T = A (+).(x) B as (present, values) in the monoid's type, every entry folded in ascending
+    k; with products=True also the Products the fold ran on.  Masks, accumulators and replace
+    are write_back's business."""
+    P = mxm_products(mul, dtype, A, B, tran0, tran1)
+    monoid = {"eq": "lxnor"}.get(monoid, monoid)
+    vals = P.fold(monoid) if P.rows.size else np.zeros(0, NP[P.dtype])
+    T = P.dense(np.ones(P.rows.size, bool), False), P.dense(vals)
+    return (T, P) if products else T
+
+
+def _column(u):
+    return u[0][:, None], u[1][:, None]
+
+
+def _row(u):
+    return u[0][None, :], u[1][None, :]
+
+
+def mxv(monoid, mul, dtype, A, u, tran0=False, products=False):
+    """w = A (+).(x) u with u an n x 1 matrix (SECONDJ = 0): the C API's definition of GrB_mxv,
+    reference docs/user_guide/operations.rst:17-22"""
+    T, P = mxm(monoid, mul, dtype, A, _column(u), tran0=tran0, products=True)
+    w = T[0][:, 0], T[1][:, 0]
+    return (w, P) if products else w
+
+
+def vxm(monoid, mul, dtype, u, A, tran1=False, products=False):
+    """w = u (+).(x) A with u a 1 x n matrix (FIRSTI = 0)"""
+    T, P = mxm(monoid, mul, dtype, _row(u), A, tran1=tran1, products=True)
+    w = T[0][0, :], T[1][0, :]
+    return (w, P) if products else w
+
+
+def order_dependent(monoid, P, seed=0):
+    """Per entry: does the fold of its products depend on their order?  Folds ascending k,
+    descending k and one seeded shuffle and compares the bits (NaNs count as equal).  Float
+    min / max return either zero when a list holds both: those entries are compared with ==."""
+    monoid = {"eq": "lxnor"}.get(monoid, monoid)
+    if P.rows.size == 0:
+        return np.zeros(0, bool)
+    a = P.fold(monoid)
+    bad = np.zeros(P.rows.size, bool)
+    loose = both_zeros(P) if monoid in ("min", "max") else bad
+    for order in ("descending", np.random.default_rng(seed)):
+        b = P.fold(monoid, P.reordered(order))
+        u = np.dtype(f"u{a.dtype.itemsize}")
+        same = a.view(u) == b.view(u)
+        if a.dtype.kind == "f":
+            same |= np.isnan(a) & np.isnan(b)
+            same |= loose & (a == b)
+        bad |= ~same
+    return bad
+
+
+def both_zeros(P):
+    """per entry of a float product: does its list hold +0.0 and -0.0?"""
+    if P.z.dtype.kind != "f" or P.rows.size == 0:
+        return np.zeros(P.rows.size, bool)
+    zero, neg = P.z == 0, np.signbit(P.z)
+    return np.logical_or.reduceat(zero & neg, P.start) & np.logical_or.reduceat(zero & ~neg, P.start)
+
+
+def zero_sign_free(monoid, P):
+    """Per entry of a float product: may a zero result carry either sign?  True where a min / max
+    monoid folds a list that holds both zeros, and where the list holds a product of a min / max
+    multiplier on +0.0 and -0.0 (C's fmin / fmax may return either; such a term can only change
+    the sign of a zero sum, product, minimum or maximum).  These entries are compared with ==."""
+    if P.z.dtype.kind != "f" or P.rows.size == 0:
+        return np.zeros(P.rows.size, bool)
+    free = np.logical_or.reduceat(P.clash, P.start)
+    return free | both_zeros(P) if monoid in ("min", "max") else free

@@ -7,6 +7,7 @@ mask cases (C = A.dup(); C(mask, accum) << A.mxm(A) and the vxm ones) do exercis
 rule, with T the recorded unmasked product, so the model's write_back runs on those.
 """
 import math
+import zlib
 
 import numpy as np
 
@@ -249,3 +250,209 @@ def test_ulp_distance():
     assert dm.ulp_distance(np.array([-0.0]), np.array([5e-324])) == 1
     assert dm.ulp_distance(np.array([np.nan, 1.0]), np.array([1.0, 1.0])) == math.inf
     assert dm.ulp_distance(np.array([np.inf]), np.array([-np.inf])) == math.inf
+
+
+# ---------------------------------------------------------------------- mxm, mxv, vxm
+def _coo_equal(got, want):
+    assert np.array_equal(got[0], want[0])
+    assert np.array_equal(got[1][got[0]], want[1][want[0]], equal_nan=got[1].dtype.kind == "f")
+
+
+def test_mxm_on_the_reference_golden_cases(golden):
+    c = golden["cases"]
+    A, v = _gold(golden["A"], (7, 7)), _gold(golden["v"], (7,))
+    pt = ("plus", "times", "INT64")
+    _coo_equal(dm.mxm(*pt, A, A), _gold(c["test_mxm"]["expected"], (7, 7)))
+    _coo_equal(dm.mxm(*pt, A, A, tran1=True), _gold(c["test_mxm_transpose_AAT"]["expected"], (7, 7)))
+    _coo_equal(dm.mxm(*pt, A, A, tran0=True), _gold(c["test_mxm_transpose_ATA"]["expected"], (7, 7)))
+    _coo_equal(dm.mxv(*pt, A, v), _gold(c["test_mxv"]["expected"], (7,)))
+    _coo_equal(dm.vxm(*pt, v, A), _gold(c["test_vxm"]["expected"], (7,)))
+    _coo_equal(dm.vxm(*pt, v, A, tran1=True), _gold(c["test_vxm_transpose"]["expected"], (7,)))
+    ns = c["test_mxm_nonsquare"]
+    p, x = dm.mxm("max", "plus", "INT64", _gold(ns["A"], (1, 5)), _gold(ns["B"], (5, 1)))
+    assert p.tolist() == [[True]] and x[0, 0] == ns["expected_scalar"]
+    vn = c["test_vxm_nonsquare"]
+    _coo_equal(dm.vxm("min", "plus", "INT64", v, _gold(vn["A"], (7, 2))), _gold(vn["expected"], (2,)))
+    # inner: u' u as 1 x n times n x 1
+    p, x = dm.mxm(*pt, (v[0][None, :], v[1][None, :]), (v[0][:, None], v[1][:, None]))
+    assert p[0, 0] and x[0, 0] == c["test_inner"]["expected_scalar"]
+    d = c["docs_mxv_plus_times"]
+    Ad = _gold(d["A"], (d["A"].get("nrows", max(d["A"]["rows"]) + 1), d["A"].get("ncols", max(d["A"]["cols"]) + 1)))
+    vd = _gold(d["v"], (Ad[0].shape[1],))
+    want = _gold(d["expected"], (Ad[0].shape[0],))
+    _coo_equal(dm.mxv("plus", "times", "FP64", (Ad[0], Ad[1].astype(float)), (vd[0], vd[1].astype(float))),
+               (want[0], want[1].astype(float)))
+
+
+def _dense_of(M):
+    r, c, x = M.to_coo()
+    return dm.to_dense((M.nrows, M.ncols), (r, c), x)
+
+
+def _dense_vec(u):
+    return dm.to_dense((u.size,), (u.indices,), u.values)
+
+
+def test_mxm_matches_the_oracle_on_the_parity_semirings():
+    import oracle as O
+    from test_gpu_parity import SEMIRINGS, _rand_csr
+
+    n, k, m = 37, 53, 41
+    for name, mon, mul, dt in SEMIRINGS:
+        rng = np.random.default_rng(zlib.crc32(repr((name, dt, "model")).encode()))
+        sr = (mon, mul, dt)
+        model = (mon.lower(), mul.lower(), dt)
+        shapes = {(False, False): ((n, k), (k, m)), (True, False): ((k, n), (k, m)),
+                  (False, True): ((n, k), (m, k)), (True, True): ((k, n), (m, k))}
+        for (t0, t1), (sa, sb) in shapes.items():
+            Ao, Bo = _rand_csr(rng, *sa, 0.15, dt), _rand_csr(rng, *sb, 0.15, dt)
+            ref = _dense_of(O.mxm(O.Csr.empty(n, m, dt), Ao, Bo, sr, tran0=t0, tran1=t1))
+            got = dm.mxm(*model, _dense_of(Ao), _dense_of(Bo), tran0=t0, tran1=t1)
+            assert got[1].dtype == dm.NP[dt]
+            if mon == "ANY":
+                assert np.array_equal(got[0], ref[0])
+            else:
+                _coo_equal(got, ref)
+        for t in (False, True):
+            Ao = _rand_csr(rng, n, k, 0.15, dt)
+            uk, un = O.Vec.from_col(_rand_csr(rng, k, 1, 0.4, dt)), O.Vec.from_col(_rand_csr(rng, n, 1, 0.4, dt))
+            u_mxv, u_vxm = (un, uk) if t else (uk, un)
+            ref_mxv = O.mxv(O.Vec(k if t else n, dt, [], []), Ao, u_mxv, sr, tran0=t)
+            ref_vxm = O.vxm(O.Vec(n if t else k, dt, [], []), u_vxm, Ao, sr, tran1=t)
+            got_mxv = dm.mxv(*model, _dense_of(Ao), _dense_vec(u_mxv), tran0=t)
+            got_vxm = dm.vxm(*model, _dense_vec(u_vxm), _dense_of(Ao), tran1=t)
+            for got, ref in ((got_mxv, ref_mxv), (got_vxm, ref_vxm)):
+                if mon == "ANY":
+                    assert np.array_equal(got[0], _dense_vec(ref)[0])
+                else:
+                    _coo_equal(got, _dense_vec(ref))
+
+
+def test_positional_multipliers_by_hand():
+    """A is 2 x 3 with A(0,1), A(0,2), A(1,0); B is 3 x 4 with B(0,2), B(1,3), B(2,0), B(2,3):
+    T(0,0) takes k = 2, T(0,3) takes k = 1, 2, T(1,2) takes k = 0"""
+    A = dm.to_dense((2, 3), ([0, 0, 1], [1, 2, 0]), np.array([9, 9, 9]))
+    B = dm.to_dense((3, 4), ([0, 1, 2, 2], [2, 3, 0, 3]), np.array([7, 7, 7, 7]))
+    want = {"firsti": (0, 0, 1), "firsti1": (1, 2, 2), "firstj": (2, 3, 0), "firstj1": (3, 5, 1),
+            "secondi": (2, 3, 0), "secondi1": (3, 5, 1), "secondj": (0, 6, 2), "secondj1": (1, 8, 3)}
+    full3, full2 = (np.ones(3, bool), np.array([4, 4, 4])), (np.ones(2, bool), np.array([4, 4]))
+    # mxv: w0 folds k = 1, 2 and w1 k = 0, with j = 0; vxm: w0 takes k = 1, w1 and w2 take k = 0, with i = 0
+    want_mxv = {"firsti": (0, 1), "firsti1": (2, 2), "firstj": (3, 0), "firstj1": (5, 1), "secondi": (3, 0),
+                "secondi1": (5, 1), "secondj": (0, 0), "secondj1": (2, 1)}
+    want_vxm = {"firsti": (0, 0, 0), "firsti1": (1, 1, 1), "firstj": (1, 0, 0), "firstj1": (2, 1, 1),
+                "secondi": (1, 0, 0), "secondi1": (2, 1, 1), "secondj": (0, 1, 2), "secondj1": (1, 2, 3)}
+    for op in dm.POSITIONAL:
+        for dt in ("INT32", "INT64"):
+            for kw, X, Y in (({}, A, B), (dict(tran0=True), dm.transpose(A), B), (dict(tran1=True), A, dm.transpose(B)),
+                             (dict(tran0=True, tran1=True), dm.transpose(A), dm.transpose(B))):
+                p, x = dm.mxm("plus", op, dt, X, Y, **kw)
+                assert x.dtype == dm.NP[dt] and p.sum() == 3
+                assert (x[0, 0], x[0, 3], x[1, 2]) == want[op], (op, kw)
+            p, x = dm.mxv("plus", op, dt, A, full3)
+            assert p.all() and tuple(x) == want_mxv[op], op
+            p, x = dm.mxv("plus", op, dt, dm.transpose(A), full3, tran0=True)
+            assert tuple(x) == want_mxv[op], op
+            p, x = dm.vxm("plus", op, dt, full2, A)
+            assert p.all() and tuple(x) == want_vxm[op], op
+            p, x = dm.vxm("plus", op, dt, full2, dm.transpose(A), tran1=True)
+            assert tuple(x) == want_vxm[op], op
+    # the lists come in ascending k
+    P = dm.mxm_products("secondi", "INT64", A, B)
+    assert P.lists()[(0, 3)].tolist() == [1, 2] and P.k.tolist() == [2, 1, 2, 0]
+    assert P.member(np.array([0, 0, 1]), np.array([3, 0, 2]), np.array([2, 3, 0])).tolist() == [True, False, True]
+
+
+def test_ordered_multipliers_by_hand():
+    """A = [[5 . 7] [. 2 .]], u = [1 10 100], v = [3 4], B = [[1 .] [. 10] [100 1000]]: an operand
+    swap anywhere in the model changes every one of these"""
+    A = dm.to_dense((2, 3), ([0, 0, 1], [0, 2, 1]), np.array([5, 7, 2]))
+    B = dm.to_dense((3, 2), ([0, 1, 2, 2], [0, 1, 0, 1]), np.array([1, 10, 100, 1000]))
+    u = np.ones(3, bool), np.array([1, 10, 100])
+    v = np.ones(2, bool), np.array([3, 4])
+    At, Bt = dm.transpose(A), dm.transpose(B)
+    want = {  # mxv A u, vxm v A, mxv A' v, mxm A B at (0,0), (0,1), (1,1)
+        "minus": ([-89, -8], [-2, 2, -4], [2, -2, 4], [-89, -993, -8]),
+        "rminus": ([89, 8], [2, -2, 4], [-2, 2, -4], [89, 993, 8]),
+        "div": ([5, 0], [0, 2, 0], [1, 0, 2], [5, 0, 0]),
+        "rdiv": ([14, 5], [1, 0, 2], [0, 2, 0], [14, 142, 5]),
+    }
+    for op, (w_mxv, w_vxm, w_mxvT, w_mxm) in want.items():
+        s = ("plus", op, "INT64")
+        assert dm.mxv(*s, A, u)[1].tolist() == w_mxv, op
+        assert dm.mxv(*s, At, u, tran0=True)[1].tolist() == w_mxv, op
+        assert dm.vxm(*s, v, A)[1].tolist() == w_vxm, op
+        assert dm.vxm(*s, v, At, tran1=True)[1].tolist() == w_vxm, op
+        assert dm.mxv(*s, At, v)[1].tolist() == w_mxvT, op
+        assert dm.mxv(*s, A, v, tran0=True)[1].tolist() == w_mxvT, op
+        for kw, X, Y in (({}, A, B), (dict(tran0=True), At, B), (dict(tran1=True), A, Bt)):
+            p, x = dm.mxm(*s, X, Y, **kw)
+            assert p.tolist() == [[True, True], [False, True]] and [x[0, 0], x[0, 1], x[1, 1]] == w_mxm, (op, kw)
+    g = ("lor", "gt", "INT64")
+    assert dm.mxv(*g, A, u)[1].tolist() == [True, False] and dm.mxv(*g, A, u)[1].dtype == np.bool_
+    assert dm.vxm(*g, v, A)[1].tolist() == [False, True, False]
+    assert dm.mxv(*g, A, v, tran0=True)[1].tolist() == [True, False, True]
+    assert dm.mxm(*g, A, Bt, tran1=True)[1].tolist() == [[True, False], [False, False]]
+    # operands are cast to the multiplier's type first: 300.7 -> INT8 127, 1.5 -> 1
+    Af = dm.to_dense((1, 2), ([0, 0], [0, 1]), np.array([300.7, 1.5]))
+    p, x = dm.mxv("plus", "times", "INT8", Af, (np.ones(2, bool), np.array([2, 3], np.int64)))
+    assert x.dtype == np.int8 and x.tolist() == [1]  # 127 * 2 + 1 * 3 = 257 wraps to 1
+
+
+def test_fold_of_all_lists_matches_the_sequential_fold():
+    rng = np.random.default_rng(11)
+    A = rng.random((9, 7)) < 0.6, rng.integers(0, 250, (9, 7)).astype(np.uint8)
+    B = rng.random((7, 8)) < 0.6, rng.integers(0, 250, (7, 8)).astype(np.uint8)
+    for mon in ("plus", "times", "min", "max", "bor", "band", "bxor", "bxnor", "lxor"):
+        (p, x), P = dm.mxm(mon, "plus", "UINT8", A, B, products=True)
+        for (i, j), z in P.lists().items():
+            assert p[i, j] and x[i, j] == dm.monoid_fold_sequential(mon, "UINT8", z), (mon, i, j)
+        assert p.sum() == len(P.lists())
+
+
+_CASES = {}
+
+
+def _sweep_case(mon, mul, dt, zt):
+    import semiring_cases as sc
+
+    key = (mon, mul, dt)
+    if key not in _CASES:
+        _CASES[key] = sc.Case(mon, mul, dt, zt)
+    return _CASES[key]
+
+
+def test_sweep_inputs_are_order_free_and_reach_terminals_and_identities():
+    """Every case of the GPU sweep, model only: Case() raises if the fold of any expected entry
+    depends on the order (ascending, descending, shuffled); every terminal value and identity
+    the multiplier can produce is the first product of an entry with more products after it."""
+    import semiring_cases as sc
+
+    tab = sc.table()
+    assert len(tab) == 210 and sum(len(v) for v in tab.values()) == 1499
+    planted = {}
+    for (mon, mul), entries in tab.items():
+        for pyname, dt, zt, names in entries:
+            case = sc.Case(mon, mul, dt, zt)
+            case.check_planted()
+            planted[(mon, mul, dt)] = len(case.planted)
+    # the plain arithmetic multipliers reach both values, the bounded ones what their range holds
+    assert planted[("min", "plus", "INT8")] == 2 and planted[("times", "minus", "UINT64")] == 2
+    assert planted[("bor", "band", "UINT64")] == 2 and planted[("land", "lxor", "BOOL")] == 2
+    assert planted[("max", "isgt", "INT8")] == 0 and planted[("times", "pair", "INT8")] == 1
+
+
+def test_zero_sign_rules_of_the_float_products():
+    pz, nz = 0.0, -0.0
+    A = dm.to_dense((1, 3), ([0, 0, 0], [0, 1, 2]), np.array([pz, 1.0, np.nan]))
+    u = np.ones(3, bool), np.array([nz, 2.0, np.nan])
+    (p, x), P = dm.mxv("plus", "max", "FP64", A, u, products=True)
+    assert P.clash.tolist() == [True, False, False] and dm.zero_sign_free("plus", P).tolist() == [True]
+    # membership for ANY: the clash zero in either sign, any NaN, but 2.0 only as itself
+    for v, ok in ((pz, True), (nz, True), (2.0, True), (-2.0, False), (-np.nan, True)):
+        assert P.member(np.array([0]), np.array([0]), np.array([v])).tolist() == [ok], v
+    (p, x), P = dm.mxv("min", "first", "FP64", A, u, products=True)
+    assert not P.clash.any() and dm.zero_sign_free("min", P).tolist() == [False]
+    B = dm.to_dense((1, 2), ([0, 0], [0, 1]), np.array([pz, nz]))
+    (p, x), P = dm.mxv("max", "first", "FP64", B, (np.ones(2, bool), np.ones(2)), products=True)
+    assert dm.zero_sign_free("max", P).tolist() == [True] and dm.zero_sign_free("plus", P).tolist() == [False]
+    assert not dm.order_dependent("max", P).any() and not dm.order_dependent("plus", P).any()
