@@ -566,6 +566,11 @@ bool gb_zpool_clear_vector(GB_Obj *v);
 void gb_select(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_IndexUnaryOp op, GB_Obj *A, const void *y, int ycode,
                const gb_desc &d);
 
+// kronecker (gb_kron.hip): T(iA p + iB, jA q + jB) = binop(A'(iA, jA), B'(iB, jB)) for every pair
+// of stored entries, written back as C<M> = C accum T
+void gb_kronecker(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_BinaryOp binop, GB_Obj *A, GB_Obj *B,
+                  const gb_desc &d);
+
 // hash Gustavson C = A*B (gb_spgemm_hash.hip): flops = per-row product counts
 void gb_spgemm_hash(gb_mat_result &T, gb_csr_view &A, gb_csr_view &B, GrB_Semiring sr, bool iso,
                     const void *av, const void *bv, const int64_t *flops);

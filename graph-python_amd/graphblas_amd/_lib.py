@@ -63,6 +63,8 @@ _SIGS = {
     "GrB_mxm": [P] * 7, "GrB_mxv": [P] * 7, "GrB_vxm": [P] * 7,
     "GrB_Matrix_eWiseMult_BinaryOp": [P] * 7, "GrB_Vector_eWiseMult_BinaryOp": [P] * 7,
     "GrB_Matrix_eWiseAdd_BinaryOp": [P] * 7, "GrB_Vector_eWiseAdd_BinaryOp": [P] * 7,
+    "GrB_Matrix_kronecker_BinaryOp": [P] * 7, "GrB_Matrix_kronecker_Monoid": [P] * 7,
+    "GrB_Matrix_kronecker_Semiring": [P] * 7,
     "GrB_Vector_assign": [P, P, P, P, P, I, P], "GrB_Matrix_assign": [P, P, P, P, P, I, P, I, P],
     "GrB_Matrix_reduce_Monoid_Scalar": [P] * 5, "GrB_Vector_reduce_Monoid_Scalar": [P] * 5,
     "GrB_transpose": [P] * 5,

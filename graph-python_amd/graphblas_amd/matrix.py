@@ -328,6 +328,9 @@ class Matrix(BaseType):
     def select(self, op, thunk=None):
         return _select_expr(self, op, thunk)
 
+    def kronecker(self, other, op=None):
+        return _kronecker(self, other, op)
+
     def isequal(self, other, *, check_dtype=False):
         """reference core/matrix.py:357-398"""
         if isinstance(other, TransposedMatrix):
@@ -537,6 +540,9 @@ class TransposedMatrix:
 
     def select(self, op, thunk=None):
         return _select_expr(self, op, thunk)
+
+    def kronecker(self, other, op=None):
+        return _kronecker(self, other, op)
 
     def to_coo(self, *args, **kw):
         r, c, v = self._matrix.to_coo(*args, **kw)
@@ -776,6 +782,26 @@ def _ewise(left, right, opobj, kind):
     cf = "GrB_Matrix_eWiseMult_BinaryOp" if kind == "mult" else "GrB_Matrix_eWiseAdd_BinaryOp"
     return MatrixExpression(f"ewise_{kind}", cf, [a, b], op=op, at=at, bt=bt, nrows=left.nrows,
                             ncols=left.ncols)
+
+
+def _kronecker(left, right, op):
+    """A.kronecker(B, op) (reference core/matrix.py:2253-2292): a BinaryOp or a Monoid ->
+    GrB_Matrix_kronecker_{BinaryOp,Monoid}; the result is (m p) x (n q)."""
+    if not isinstance(right, (Matrix, TransposedMatrix)):
+        raise TypeError(f"Bad type for argument `other` in kronecker: expected Matrix or TransposedMatrix, got "
+                        f"{type(right).__name__}")
+    if op is None:
+        op = _op.binary.times
+    op = _op.get_typed_op(op, left.dtype, right.dtype, kind="binary")
+    # Per the spec, op may be a semiring, but this is weird, so don't.
+    if op.opclass not in ("BinaryOp", "Monoid"):
+        raise TypeError(f"Bad type for argument `op` in kronecker: expected BinaryOp or Monoid, got {op.opclass}")
+    if getattr(op, "is_positional", False):
+        raise NotImplementedError("positional operators in kronecker")
+    a, at = _unwrap(left)
+    b, bt = _unwrap(right)
+    return MatrixExpression("kronecker", f"GrB_Matrix_kronecker_{op.opclass}", [a, b], op=op, at=at, bt=bt,
+                            nrows=left.nrows * right.nrows, ncols=left.ncols * right.ncols)
 
 
 class MatrixExpression(BaseExpression):

@@ -316,6 +316,21 @@ GrB_Info GrB_Matrix_select_Scalar(GrB_Matrix C, const GrB_Matrix Mask, const GrB
 GrB_Info GrB_Vector_select_Scalar(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum,
                                   const GrB_IndexUnaryOp op, const GrB_Vector u, const GrB_Scalar y,
                                   const GrB_Descriptor desc);
+/* kronecker (reference core/matrix.py:2253-2292): C<M> = accum(C, kron(A', B')).  With A' m x n
+ * and B' p x q (after GrB_INP0 / GrB_INP1), every pair of stored entries gives
+ * T(iA p + iB, jA q + jB) = op(A'(iA, jA), B'(iB, jB)): the operands are cast to the operator's
+ * input type, T has its output type, computed zeros stay stored (nvals(T) = nvals(A) nvals(B)),
+ * and C must be (m p) x (n q).  The Monoid form uses the monoid's binary operator, the Semiring
+ * form the semiring's multiplier.  Positional operators are GrB_NOT_IMPLEMENTED. */
+GrB_Info GrB_Matrix_kronecker_BinaryOp(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum,
+                                       const GrB_BinaryOp op, const GrB_Matrix A, const GrB_Matrix B,
+                                       const GrB_Descriptor desc);
+GrB_Info GrB_Matrix_kronecker_Monoid(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum,
+                                     const GrB_Monoid op, const GrB_Matrix A, const GrB_Matrix B,
+                                     const GrB_Descriptor desc);
+GrB_Info GrB_Matrix_kronecker_Semiring(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum,
+                                       const GrB_Semiring op, const GrB_Matrix A, const GrB_Matrix B,
+                                       const GrB_Descriptor desc);
 
 /* ---------------------------------------------------------------- the hot path */
 /* C<Mask> = C accum (A' (+).(x) B')      replaces SuiteSparse GrB_mxm */
@@ -495,7 +510,8 @@ GrB_Info GxB_Matrix_prepare_transpose(GrB_Matrix A);
 GrB_Info GxB_MatrixMarket_read_coo(const char *path, GrB_Index *nrows, GrB_Index *ncols, GrB_Index *nvals,
                                    int *type_code, GrB_Index **I, GrB_Index **J, void **X);
 GrB_Info GxB_MatrixMarket_free(void *p);
-/* Backend selection knobs for benchmarking ablations: 0 = automatic.  get_int also reads
+/* Backend selection knobs for benchmarking ablations: 0 = automatic ("kron_method": 1 = one
+ * thread per output row in GrB_kronecker).  get_int also reads
  * the read-only counters "stat_bfs_spec_adopted" / "stat_bfs_spec_rollbacks" (BFS level
  * speculation) and "stat_nvals_copy" (vector counts read by a device copy
  * instead of the producing kernel's host mailbox). */
