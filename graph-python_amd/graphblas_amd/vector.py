@@ -199,7 +199,8 @@ class Vector(BaseType):
         """w(mask, accum, replace)[I] = value  (GrB_Vector_assign[_T], GrB_ALL for ':')."""
         from .scalar import Scalar
 
-        if keys is Ellipsis or keys == slice(None):
+        # (an index array must not reach `==`: comparing it with a slice is elementwise)
+        if keys is Ellipsis or (isinstance(keys, slice) and keys == slice(None)):
             idx, ni = lib.GrB_ALL, self._size
             idx_obj = None
         else:

@@ -1,5 +1,6 @@
 """A dense numpy model of the general GraphBLAS operations (eWise, apply, reduce,
-transpose, build and the output write-back), written from the GraphBLAS C API
+transpose, build, the output write-back, and the indexing operations extract, assign,
+setElement, removeElement and resize), written from the GraphBLAS C API
 rules and the SuiteSparse:GraphBLAS 7.4 builtin definitions, not from the
 kernels.  A sparse object is a ``(present, values)`` pair of arrays of the
 object's shape; dtypes are the GraphBLAS names ("INT8", "FP64", ...).
@@ -616,3 +617,91 @@ def zero_sign_free(monoid, P):
         return np.zeros(P.rows.size, bool)
     free = np.logical_or.reduceat(P.clash, P.start)
     return free | both_zeros(P) if monoid in ("min", "max") else free
+
+
+# ---------------------------------------------------------------------- indexing operations
+# Written from the GraphBLAS C API 2.0 text: GrB_extract (section 4.3.6), GrB_assign (4.3.7),
+# setElement / removeElement (4.2.x) and resize.  Index lists are int arrays; None is GrB_ALL.
+def _index(I, n):
+    return np.arange(n, dtype=np.int64) if I is None else np.asarray(I, np.int64).reshape(-1)
+
+
+def extract(A, I=None, J=None):
+    """T(r, c) = A(I[r], J[c]); the lists may repeat and come in any order"""
+    p, v = A
+    sel = np.ix_(_index(I, p.shape[0]), _index(J, p.shape[1]))
+    return p[sel].copy(), v[sel].copy()
+
+
+def extract_vec(u, I=None):
+    """t(k) = u(I[k])"""
+    p, v = u
+    I = _index(I, p.shape[0])
+    return p[I].copy(), v[I].copy()
+
+
+def is_scalar(A):
+    return not isinstance(A, tuple)
+
+
+def assign(C, A, I=None, J=None, mask=None, mask_comp=False, mask_struct=False, replace=False, accum=None,
+           accum_dtype=None):
+    """GrB_assign (not subassign) C<M, replace>(I, J) = accum(C(I, J), A) for a matrix or, with
+    J None, a vector.  A is a model object of the region's shape (duplicate-free lists), a numpy
+    scalar assigned to every position of the region (lists may repeat), or None: the empty scalar.
+    Z = C; inside the region Z = accum(C, A) on the union, or without accum Z = A there (entries
+    of C that A lacks are deleted).  Then C<M, replace> = Z over the whole of C: the mask has C's
+    shape and `replace` deletes outside the region too."""
+    cp, cv = C
+    ct = name_of(cv.dtype)
+    lists = [_index(I, cp.shape[0])] + ([_index(J, cp.shape[1])] if cp.ndim == 2 else [])
+    sel = np.ix_(*lists)
+    region = np.zeros(cp.shape, bool)
+    region[sel] = True
+    if A is None:
+        tp, tv = np.zeros(cp.shape, bool), np.zeros(cp.shape, NP[ct])
+    elif is_scalar(A):
+        x = np.asarray(A)
+        tp, tv = region, np.where(region, x, x.dtype.type(0))
+    else:
+        ap, av = A
+        assert ap.shape == tuple(l.size for l in lists), "A must have the shape of the region"
+        assert all(np.unique(l).size == l.size for l in lists), "duplicates are undefined for object assign"
+        tp, tv = np.zeros(cp.shape, bool), np.zeros(cp.shape, av.dtype)
+        tp[sel], tv[sel] = ap, av
+    if accum is None:
+        zp, zv = np.where(region, tp, cp), np.where(region, cast(tv, ct), cv)
+    else:  # outside the region T is empty and C is kept
+        zp, zv = write_back(C, (tp, tv), accum=accum, accum_dtype=accum_dtype)
+    zv = np.where(zp, zv, NP[ct](0))
+    return write_back(C, (zp, zv), mask=mask, mask_comp=mask_comp, mask_struct=mask_struct, replace=replace)
+
+
+def assign_vec(w, u, I=None, **kw):
+    assert w[0].ndim == 1
+    return assign(w, u, I, None, **kw)
+
+
+def set_element(A, index, x):
+    """A(index) = x cast to A's type; index is an int (vector) or an (i, j) pair"""
+    p, v = A[0].copy(), A[1].copy()
+    p[index] = True
+    v[index] = cast(np.asarray(x).reshape(1), name_of(v.dtype))[0]
+    return p, v
+
+
+def remove_element(A, index):
+    p, v = A[0].copy(), A[1].copy()
+    p[index] = False
+    v[index] = 0
+    return p, v
+
+
+def resize(A, shape):
+    """shrinking drops the entries outside the new shape; growing adds none"""
+    p, v = A
+    shape = (shape,) if np.ndim(shape) == 0 else tuple(shape)
+    np_, nv = np.zeros(shape, bool), np.zeros(shape, v.dtype)
+    keep = tuple(slice(0, min(a, b)) for a, b in zip(shape, p.shape))
+    np_[keep], nv[keep] = p[keep], v[keep]
+    return np_, nv

@@ -5,6 +5,11 @@ to agree quietly with a wrong kernel.
 The golden file records no eWise, apply, reduce or transpose case of the reference; its accum and
 mask cases (C = A.dup(); C(mask, accum) << A.mxm(A) and the vxm ones) do exercise the write-back
 rule, with T the recorded unmasked product, so the model's write_back runs on those.
+
+The indexing functions (extract, assign, set_element, remove_element, resize) are pinned by
+hand-worked cases, by the expectations test_extract.py and test_scalar_args.py state, and by
+the reference's own extract / assign / resize / delete cases of golden/indexing_golden.json;
+the last test builds the expectation of every case of test_indexing_gpu.py.
 """
 import math
 import zlib
@@ -456,3 +461,224 @@ def test_zero_sign_rules_of_the_float_products():
     (p, x), P = dm.mxv("max", "first", "FP64", B, (np.ones(2, bool), np.ones(2)), products=True)
     assert dm.zero_sign_free("max", P).tolist() == [True] and dm.zero_sign_free("plus", P).tolist() == [False]
     assert not dm.order_dependent("max", P).any() and not dm.order_dependent("plus", P).any()
+
+
+# ---------------------------------------------------------------------- indexing operations
+def _vec(d, n, dtype=np.int64):
+    return dm.to_dense((n,), (list(d),), np.array(list(d.values()), dtype))
+
+
+def _vdict(w):
+    i, x = dm.to_coo(w)
+    return dict(zip(i.tolist(), x.tolist()))
+
+
+def _mdict(C):
+    r, c, x = dm.to_coo(C)
+    return {(a, b): y for a, b, y in zip(r.tolist(), c.tolist(), x.tolist())}
+
+
+def test_extract_set_remove_resize_by_hand():
+    """A = [[1 . 3] [. 5 .]]: T(r, c) = A(I[r], J[c]) with repeats and any order"""
+    A = dm.to_dense((2, 3), ([0, 0, 1], [0, 2, 1]), np.array([1, 3, 5], np.int16))
+    T = dm.extract(A, [1, 0, 1], [2, 2, 0, 1])
+    assert T[1].dtype == np.int16 and T[0].shape == (3, 4)
+    assert _mdict(T) == {(0, 3): 5, (1, 0): 3, (1, 1): 3, (1, 2): 1, (2, 3): 5}
+    assert _mdict(dm.extract(A)) == _mdict(A) and dm.extract(A, [], None)[0].shape == (0, 3)
+    assert _mdict(dm.extract(A, None, [1])) == {(1, 0): 5}
+    u = _vec({1: 10, 2: 20}, 4)
+    assert _vdict(dm.extract_vec(u, [2, 2, 0, 1])) == {0: 20, 1: 20, 3: 10}
+    assert _vdict(dm.extract_vec(u)) == {1: 10, 2: 20}
+    # setElement casts to the object's type; removeElement of an absent entry changes nothing
+    B = dm.set_element(A, (1, 2), 300.7)
+    assert B[1].dtype == np.int16 and _mdict(B) == {(0, 0): 1, (0, 2): 3, (1, 1): 5, (1, 2): 300}
+    assert _mdict(A) == {(0, 0): 1, (0, 2): 3, (1, 1): 5}  # the input is not edited
+    assert _mdict(dm.set_element(A, (0, 0), -7)) == {(0, 0): -7, (0, 2): 3, (1, 1): 5}
+    assert _mdict(dm.remove_element(A, (0, 2))) == {(0, 0): 1, (1, 1): 5}
+    assert _mdict(dm.remove_element(A, (1, 0))) == _mdict(A)
+    assert _vdict(dm.set_element(_vec({}, 3, np.uint8), 2, -1)) == {2: 255}
+    # resize: shrinking drops, growing adds nothing, and what was dropped does not come back
+    assert _mdict(dm.resize(A, (1, 3))) == {(0, 0): 1, (0, 2): 3}
+    assert _mdict(dm.resize(A, (2, 2))) == {(0, 0): 1, (1, 1): 5}
+    assert _mdict(dm.resize(A, (5, 7))) == _mdict(A) and dm.resize(A, (5, 7))[0].shape == (5, 7)
+    assert dm.resize(A, (0, 0))[0].shape == (0, 0) and dm.resize(A, (0, 3))[0].shape == (0, 3)
+    assert _mdict(dm.resize(dm.resize(A, (2, 2)), (2, 3))) == {(0, 0): 1, (1, 1): 5}
+    assert _vdict(dm.resize(dm.resize(u, 2), 4)) == {1: 10}
+
+
+def test_assign_by_hand():
+    """GrB_assign, not subassign: the mask has C's size and replace reaches outside the region"""
+    C = _vec({0: 100, 1: 101, 2: 102, 4: 104}, 6)
+    u = _vec({0: -1, 2: -3}, 3)
+    I = [4, 1, 3]  # w(4) = u(0), w(1) = u(1), w(3) = u(2)
+    assert _vdict(dm.assign_vec(C, u, I)) == {0: 100, 2: 102, 3: -3, 4: -1}  # 1 is deleted
+    assert _vdict(dm.assign_vec(C, u, I, accum="plus")) == {0: 100, 1: 101, 2: 102, 3: -3, 4: 103}
+    M = dm.to_dense((6,), ([0, 1, 3],), np.array([True, False, True]))
+    assert _vdict(dm.assign_vec(C, u, I, mask=M, mask_struct=True)) == {0: 100, 2: 102, 3: -3, 4: 104}
+    assert _vdict(dm.assign_vec(C, u, I, mask=M)) == {0: 100, 1: 101, 2: 102, 3: -3, 4: 104}
+    # replace deletes outside the mask, outside the region too (index 2 and 4)
+    assert _vdict(dm.assign_vec(C, u, I, mask=M, mask_struct=True, replace=True)) == {0: 100, 3: -3}
+    assert _vdict(dm.assign_vec(C, u, I, mask=M, mask_comp=True, replace=True)) == {2: 102, 4: -1}
+    # scalars: repeats in the list are fine; an empty scalar deletes (nothing under accum)
+    assert _vdict(dm.assign_vec(C, np.int64(7), [1, 1, 5])) == {0: 100, 1: 7, 2: 102, 4: 104, 5: 7}
+    assert _vdict(dm.assign_vec(C, np.int64(7), [1, 1, 5], accum="plus")) == {0: 100, 1: 108, 2: 102, 4: 104, 5: 7}
+    assert _vdict(dm.assign_vec(C, None, [1, 1, 5])) == {0: 100, 2: 102, 4: 104}
+    assert _vdict(dm.assign_vec(C, None, [1, 1, 5], accum="plus")) == _vdict(C)
+    assert _vdict(dm.assign_vec(C, np.float64(np.nan), None, mask=M)) == {0: 0, 1: 101, 2: 102, 3: 0, 4: 104}
+    assert _vdict(dm.assign_vec(_vec({1: 5}, 3, np.int8), np.float64(1e30), None)) == {0: 127, 1: 127, 2: 127}
+    # the accumulator runs in its own type: 2^53 + 1 survives INT64 plus, not FP64 plus
+    big = _vec({0: 2**53}, 1)
+    assert _vdict(dm.assign_vec(big, np.int64(1), None, accum="plus")) == {0: 2**53 + 1}
+    assert _vdict(dm.assign_vec(big, np.int64(1), None, accum="plus", accum_dtype="FP64")) == {0: 2**53}
+    # matrices: the region is I x J
+    A = dm.to_dense((3, 3), ([0, 1, 1, 2], [0, 0, 1, 2]), np.array([1, 2, 3, 4]))
+    S = dm.to_dense((2, 2), ([0], [1]), np.array([9]))
+    assert _mdict(dm.assign(A, S, [1, 2], [0, 2])) == {(0, 0): 1, (1, 1): 3, (1, 2): 9}
+    assert _mdict(dm.assign(A, S, [1, 2], [0, 2], accum="second")) == {(0, 0): 1, (1, 0): 2, (1, 1): 3, (1, 2): 9,
+                                                                       (2, 2): 4}
+    assert _mdict(dm.assign(A, np.int64(0), None, [1])) == {(0, 0): 1, (0, 1): 0, (1, 0): 2, (1, 1): 0, (2, 1): 0,
+                                                           (2, 2): 4}
+    assert _mdict(dm.assign(A, np.int64(5), [], None)) == _mdict(A)
+
+
+def test_assign_restates_the_device_tests():
+    """the expectations test_extract.py::test_vector_index_assign_replaces_region and
+    test_scalar_args.py state as dictionaries, from the model"""
+    n = 12
+    w = _vec({k: k + 100 for k in range(n)}, n)
+    u = _vec({0: -1, 2: -3}, 4)
+    I = [1, 3, 5, 7]
+    exp = {k: k + 100 for k in range(n) if k not in (3, 7)}
+    exp.update({1: -1, 5: -3})
+    assert _vdict(dm.assign_vec(w, u, I)) == exp  # the region delete
+    m = dm.to_dense((n,), ([3, 5],), np.array([True, True]))
+    exp = {k: k + 100 for k in range(n) if k != 3}
+    exp[5] = -3
+    assert _vdict(dm.assign_vec(w, u, I, mask=m, mask_struct=True)) == exp
+    exp = {k: k + 100 for k in range(n)}
+    exp[1] += -1
+    exp[5] += -3
+    assert _vdict(dm.assign_vec(w, u, I, accum="plus")) == exp
+    keep = [k for k in range(n) if k != 5]
+    w4 = _vec({k: k + 100 for k in keep}, n)
+    exp = {k: k + 100 for k in keep if k not in (3, 7)}
+    exp[1] = -1
+    assert _vdict(dm.assign_vec(w4, u, I, mask=w4, mask_struct=True)) == exp  # the mask aliases the output
+    vals = np.arange(n) + 100
+    vals[1] = 0
+    w5 = np.ones(n, bool), vals
+    exp = {k: int(vals[k]) for k in range(n) if k not in (3, 7)}
+    exp[5] = -3
+    assert _vdict(dm.assign_vec(w5, u, I, mask=w5)) == exp  # value mask: 1 holds 0 and keeps it
+    # test_scalar_args.py::test_vector_assign_scalar
+    base = {k: 100 + k for k in range(0, 10, 2)}
+    w, I = _vec(base, 10), [0, 1, 2, 3, 4, 5]
+    m = dm.to_dense((10,), ([1, 2, 3, 8],), np.ones(4, bool))
+    S = dict(mask=m, mask_struct=True)
+    exp = dict(base)
+    exp.update({1: -5, 2: -5, 3: -5})
+    assert _vdict(dm.assign_vec(w, np.int32(-5), I, **S)) == exp
+    assert _vdict(dm.assign_vec(w, None, I, **S)) == {k: x for k, x in base.items() if k != 2}
+    assert _vdict(dm.assign_vec(w, None, I)) == {k: x for k, x in base.items() if k > 5}
+    assert _vdict(dm.assign_vec(w, None, I, accum="plus")) == base
+    assert _vdict(dm.assign_vec(w, None, None, mask_comp=True, replace=True, **S)) == {}
+    exp = {k: -5 for k in range(10) if k not in (1, 2, 3, 8)}
+    exp[2], exp[8] = base[2], base[8]
+    assert _vdict(dm.assign_vec(w, np.int32(-5), None, mask_comp=True, **S)) == exp
+    # test_scalar_args.py::test_matrix_assign_scalar
+    rng = np.random.default_rng(5)
+    have, vals = rng.random((7, 9)) < 0.5, rng.integers(1, 50, (7, 9))
+    mhave = rng.random((7, 9)) < 0.5
+    C, M = (have, np.where(have, vals, 0)), (mhave, mhave.copy())
+    Il, Jl = [1, 3, 4, 6], [0, 2, 5, 7, 8]
+    region = np.zeros((7, 9), bool)
+    region[np.ix_(Il, Jl)] = True
+    sel = region & mhave
+    S = dict(mask=M, mask_struct=True)
+    p, v = dm.assign(C, np.int64(77), Il, Jl, **S)
+    assert np.array_equal(p, have | sel) and np.array_equal(v[p], np.where(sel, 77, vals)[p])
+    assert np.array_equal(dm.assign(C, None, Il, Jl, **S)[0], have & ~sel)
+    assert np.array_equal(dm.assign(C, None, Il, Jl, mask_comp=True, replace=True, **S)[0],
+                          have & ~(region & ~mhave) & ~mhave)
+    assert np.array_equal(dm.assign(C, None, Il, Jl, accum="plus")[0], have)
+    assert not dm.assign(C, None, None, None)[0].any()
+
+
+def test_indexing_golden_cases():
+    """the reference's own extract / assign / resize / delete expectations (indexing_golden.json)"""
+    import json
+    import os
+
+    with open(os.path.join(os.path.dirname(__file__), "golden", "indexing_golden.json")) as f:
+        g = json.load(f)
+    V = lambda d: dm.to_dense((d["size"],), (d["indices"],), np.array(d["values"], np.int64))
+    Mx = lambda d: dm.to_dense((d["nrows"], d["ncols"]), (d["rows"], d["cols"]), np.array(d["values"], np.int64))
+    same = lambda a, b: a[0].shape == b[0].shape and np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    v, A, c = V(g["v"]), Mx(g["A"]), g["cases"]
+    w = v
+    for step in c["vector_resize"]["steps"]:
+        w = dm.resize(w, step["size"])
+        assert w[0].sum() == step["nvals"] and not w[0][step.get("absent", 0)]
+    assert same(w, V(c["vector_resize"]["expected_last"]))
+    assert same(dm.remove_element(v, c["vector_remove_element"]["remove"]), V(c["vector_remove_element"]["expected"]))
+    assert same(dm.extract_vec(v, c["vector_extract"]["I"]), V(c["vector_extract"]["expected"]))
+    k = c["vector_assign"]
+    assert same(dm.assign_vec(v, V(k["u"]), k["I"]), V(k["expected"]))
+    k = c["vector_assign_scalar"]
+    assert same(dm.assign_vec(v, np.int64(k["x"]), k["I"]), V(k["expected"]))
+    k = c["vector_assign_scalar_mask"]
+    for kind, want in k["expected"].items():
+        got = dm.assign_vec(v, np.int64(k["x"]), None, mask=V(k["mask"]), mask_struct="S" in kind,
+                            mask_comp=kind.startswith("~"))
+        assert same(got, V(want)), kind
+    k = c["vector_delete_via_scalar"]
+    w = dm.assign_vec(v, None, k["I"])
+    assert same(w, V(k["expected"])) and dm.assign_vec(w, None, None)[0].sum() == k["then_all_nvals"]
+    C = A
+    for step in c["matrix_resize"]["steps"]:
+        C = dm.resize(C, step["shape"])
+        assert C[0].sum() == step["nvals"] and ("absent" not in step or not C[0][tuple(step["absent"])])
+    assert same(C, Mx(c["matrix_resize"]["expected_last"]))
+    k = c["matrix_remove_element"]
+    C = dm.remove_element(A, tuple(k["remove"]))
+    assert not C[0][tuple(k["absent"])] and C[1][tuple(k["kept"]["index"])] == k["kept"]["value"]
+    assert C[0].sum() == k["nvals"]
+    k = c["matrix_extract"]
+    assert same(dm.extract(A, k["I"], k["J"]), Mx(k["expected"]))
+    k = c["matrix_extract_row"]
+    row = dm.extract(A, [k["i"]], k["J"])
+    assert same((row[0][0], row[1][0]), V(k["expected"]))
+    At = dm.transpose(A)  # the same through A.T[J, i]
+    col = dm.extract(At, k["J"], [k["i"]])
+    assert same((col[0][:, 0], col[1][:, 0]), V(k["expected"]))
+    k = c["matrix_extract_column"]
+    col = dm.extract(A, k["I"], [k["j"]])
+    assert same((col[0][:, 0], col[1][:, 0]), V(k["expected"]))
+    k = c["matrix_assign_scalar"]
+    assert same(dm.assign(A, np.int64(k["x"]), k["I"], k["J"]), Mx(k["expected"]))
+    C = A
+    for step in c["matrix_delete_via_scalar"]["steps"]:
+        C = dm.assign(C, None, step["I"], step["J"])
+        assert C[0].sum() == step["nvals"]
+
+
+def test_indexing_case_tables_build_every_expectation():
+    """Every case of test_indexing_gpu.py, model only: the tables hold what the issue lists
+    (assert_coverage) and each expectation builds, has the output's shape and type, and differs
+    from the untouched output where the case is meant to change something."""
+    import indexing_cases as ic
+
+    ic.assert_coverage()
+    total = changed = 0
+    for op in ic.OPS:
+        for c in ic.cases(op):
+            B = ic.build(c)
+            total += 1
+            before = getattr(B, "C", None) if hasattr(B, "C") else getattr(B, "w", None)
+            if before is not None:
+                assert B.want[0].shape == before[0].shape and B.want[1].dtype == before[1].dtype, c.id
+                changed += not (np.array_equal(B.want[0], before[0]) and
+                                np.array_equal(B.want[1], before[1], equal_nan=B.want[1].dtype.kind == "f"))
+            assert not B.want[1][~B.want[0]].any(), c.id  # absent cells carry no value
+    assert total == ic.CASE_COUNT, total
+    assert changed > total // 2
