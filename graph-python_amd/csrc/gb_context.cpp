@@ -409,7 +409,7 @@ int64_t gb_read_i64(const int64_t *dptr) {
     return v;
 }
 
-int64_t gb_iso_ts_dump();  // gb_mxv.hip (diagnostics)
+int64_t gb_iso_ts_dump();  // gb_spmv_iso.hip (diagnostics)
 
 static const char *k_type_names[] = {"BOOL", "INT8", "UINT8", "INT16", "UINT16", "INT32",
                                      "UINT32", "INT64", "UINT64", "FP32", "FP64"};
@@ -527,7 +527,7 @@ GrB_Info GxB_Global_get_int(const char *key, int64_t *value) {
         *value = g_stat_nvals_copy.load(std::memory_order_relaxed);
         return GrB_SUCCESS;
     }
-    if (!strcmp(key, "iso_ts_dump")) {  // diagnostics: GRAPHBLAS_AMD_ISO_TS (gb_mxv.hip)
+    if (!strcmp(key, "iso_ts_dump")) {  // diagnostics: GRAPHBLAS_AMD_ISO_TS (gb_spmv_iso.hip)
         return gb_api(nullptr, [&] { *value = gb_iso_ts_dump(); });
     }
     // named kernel-class counters (gb_stat_add): "stat_" + name; 0 before the first count

@@ -77,6 +77,40 @@ extern const GB_builtin_entry GB_builtin_registry[];
 
 enum { GB_KIND_MATRIX = 0, GB_KIND_VECTOR = 1, GB_KIND_SCALAR = 2 };
 
+// Per-orientation caches of a matrix, attached lazily by the gb_view_* builders and freed
+// together by gb_orient_cache_drop (gb_object.hip), which frees the device pointers and
+// resets every field to the defaults below.
+struct gb_orient_cache {
+    // hub-chunk table, built by gb_view_hubs (gb_mxv.hip)
+    int32_t *hub_tab = nullptr;
+    int64_t hub_n = 0, hub_H = 0;
+    // bitmap of the non-empty rows
+    uint64_t *rows_ne = nullptr;
+    // pull heads (gb_view_pullfirst, gb_mxv.hip):
+    // per row 4 int32 -- its neighbours with the most entries in the other orientation
+    // first, the whole row when it has at most 4 (padding -1), else 3 of them and -2 -- and
+    // the row's own length in the other orientation (saturated to 32 bits)
+    int32_t *phead = nullptr;
+    uint32_t *pdeg = nullptr;
+    int64_t maxdeg = -1;  // longest row (host), built with the hub table; -1 unknown
+    // long-row chunk table (general SpMV, gb_mxv.hip)
+    int32_t *long_tab = nullptr;
+    int64_t long_n = 0;
+    // hot-column relabel (general SpMV with a dense input, gb_prim.hip gb_view_hot):
+    // colidx with the hot_n most frequent columns replaced by INT32_MIN | rank (rank in
+    // descending frequency), and the hot columns' original ids in rank order
+    int32_t *hot_ci = nullptr;
+    int32_t *hot_cols = nullptr;
+    int64_t hot_n = 0;
+    // narrow copy of the integer values, when every
+    // value fits fewer bytes (gb_prim.hip gb_view_narrow): nar_k = 1/2/4 unsigned, -1/-2/-4
+    // signed bytes per value, 0 not narrowable; nar_done: computed
+    void *nar_vx = nullptr;
+    int nar_k = 0;
+    bool nar_done = false;
+};
+void gb_orient_cache_drop(gb_orient_cache &c);
+
 // Device storage.  CSR for matrices; bitmap + dense values for vectors/scalars.
 struct GB_Matrix_opaque {
     uint64_t magic;
@@ -95,34 +129,8 @@ struct GB_Matrix_opaque {
     int32_t *t_colidx;
     void *t_vals;
     int64_t *t_perm;     // CSC position -> CSR position of the same entry
-    // cached hub-chunk tables of the CSR (0) and CSC (1) orientation, built by
-    // gb_view_hubs (gb_mxv.hip); dropped with the transpose
-    int32_t *hub_tab[2];
-    int64_t hub_n[2], hub_H[2];
-    // cached bitmaps of the non-empty rows of the CSR (0) / CSC (1)
-    uint64_t *rows_ne[2];
-    // cached pull heads of the CSR (0) / CSC (1) orientation (gb_view_pullfirst, gb_mxv.hip):
-    // per row 4 int32 -- its neighbours with the most entries in the other orientation
-    // first, the whole row when it has at most 4 (padding -1), else 3 of them and -2 -- and
-    // the row's own length in the other orientation (saturated to 32 bits)
-    int32_t *phead[2];
-    uint32_t *pdeg[2];
-    int64_t maxdeg[2];   // longest row of each orientation (host), built with the hub tables; -1 unknown
-    // cached long-row chunk tables (general SpMV, gb_mxv.hip)
-    int32_t *long_tab[2];
-    int64_t long_n[2];
-    // cached hot-column relabel (general SpMV with a dense input, gb_prim.hip gb_view_hot):
-    // colidx with the hot_n most frequent columns replaced by INT32_MIN | rank (rank in
-    // descending frequency), and the hot columns' original ids in rank order
-    int32_t *hot_ci[2];
-    int32_t *hot_cols[2];
-    int64_t hot_n[2];
-    // cached narrow copy of the integer values of the CSR (0) / CSC (1) orientation, when every
-    // value fits fewer bytes (gb_prim.hip gb_view_narrow): nar_k = 1/2/4 unsigned, -1/-2/-4
-    // signed bytes per value, 0 not narrowable; nar_done: computed
-    void *nar_vx[2];
-    int nar_k[2];
-    bool nar_done[2];
+    // what the kernels cache about the CSR (0) and the CSC (1) orientation; dropped with the transpose
+    gb_orient_cache oc[2];
     // ---- bitmap (kind == VECTOR / SCALAR); length n = nrows (ncols == 1)
     uint64_t *bits;      // [ceil(n/64)]
     void *dense;         // [n] or [1] when iso
@@ -196,7 +204,7 @@ struct gb_spec_hold_guard {
 };
 // A pending root (gb_object.hip): `GrB_Vector_setElement_BOOL(q, true, i)` on an empty BOOL vector
 // -- the BFS start, notebooks/Example B.1 cell 8 -- is recorded instead of launched; the level
-// SpMV of the notebook shape that reads q consumes it (its kernel pushes from vertex i, gb_mxv.hip
+// SpMV of the notebook shape that reads q consumes it (its kernel pushes from vertex i, gb_spmv_iso.hip
 // gb_push_root), and the deferred stamp `v<q> = 1` before it keeps it pending (g_root_hold); any
 // other API call materialises it first (gb_root_flush: the single-thread set launch it replaced).
 extern std::atomic<bool> g_root_active;
@@ -369,14 +377,14 @@ struct gb_csr_view {
     const int32_t *hubs = nullptr;
     int64_t nhubs = 0, hub_H = 0;
     const uint64_t *nonempty = nullptr;  // bitmap of rows with entries (when attached)
-    const int32_t *phead = nullptr;      // pull head per row, 4 int32 (when attached; see GB_Obj)
+    const int32_t *phead = nullptr;      // pull head per row, 4 int32 (when attached; see gb_orient_cache)
     const uint32_t *pdeg = nullptr;      // row length in the other orientation (when attached)
     int64_t maxdeg = -1;                 // longest row (host; attached with the hub chunks, -1 unknown)
     const int32_t *lchunks = nullptr;    // long-row chunks (row, piece) of the general SpMV (when attached)
     int64_t nlchunks = -1;
-    const void *nvx = nullptr;           // narrow copy of vals (when attached; see GB_Obj::nar_vx)
+    const void *nvx = nullptr;           // narrow copy of vals (when attached; see gb_orient_cache::nar_vx)
     int nvk = 0;                         // its kind: 1/2/4 unsigned, -1/-2/-4 signed bytes, 0 none
-    const int32_t *hcolidx = nullptr;    // hot-column relabelled colidx (when attached; see GB_Obj::hot_ci)
+    const int32_t *hcolidx = nullptr;    // hot-column relabelled colidx (when attached; see gb_orient_cache::hot_ci)
     const int32_t *hcols = nullptr;      // the hot columns' original ids, rank order
     int64_t nhot = 0;
     gb_scratch own;
@@ -527,7 +535,7 @@ bool gb_writeback_vector(GB_Obj *C, gb_vec_result &T, GB_Obj *M, const gb_desc &
 void gb_writeback_matrix(GB_Obj *C, gb_mat_result &T, GB_Obj *M, const gb_desc &d,
                          GrB_BinaryOp accum);
 
-// kernels of the hot path (gb_mxv.hip, gb_mxm.hip)
+// kernels of the hot path (gb_mxv.hip, gb_spmv_iso.hip, gb_mxm.hip)
 // A: rows = output positions (pull); Apush: the other orientation (rows = u's
 // positions) or nullptr; the device picks push or pull per call.
 // A deferred `w<q>(:) = x` (GrB_Vector_assign with a value or structural mask q,
@@ -553,9 +561,16 @@ struct gb_asg {
 void gb_spmv(gb_vec_result &T, const gb_csr_view &A, const gb_csr_view *Apush, gb_bitmap_view &u,
              const gb_vmask &mask, GrB_Semiring sr, bool flip, const gb_asg *asg = nullptr);
 bool gb_spmv_result_iso(GrB_Semiring sr, bool a_iso, bool u_iso, bool flip);
+// the iso-result (BFS) SpMV (gb_spmv_iso.hip), called by gb_spmv once T is allocated and n > 0;
+// av / uv: the operands' values as the multiplier's input type (nullptr: not read)
+void gb_spmv_iso(gb_vec_result &T, const gb_csr_view &A, const gb_csr_view *Apush, gb_bitmap_view &u,
+                 const gb_vmask &mask, GrB_Semiring sr, bool flip, const gb_asg *asg, const void *av,
+                 const void *uv);
+#define SPMV_BLOCK 256  // threads per block of the SpMV kernels of both files
+#define WAVES_PER_BLOCK (SPMV_BLOCK / 64)
 void gb_spgemm(gb_mat_result &T, gb_csr_view &A, gb_csr_view &B, gb_csr_view *BT,
                gb_mmask &mask, GrB_Semiring sr);
-// Vector clears without a launch (gb_mxv.hip): a cleared vector takes a pre-zeroed bitmap and
+// Vector clears without a launch (gb_spmv_iso.hip): a cleared vector takes a pre-zeroed bitmap and
 // count from a small pool; its old bitmap is zeroed by the next iso SpMV launch and returns to
 // the pool.  Returns false (nothing changed but the old bitmap possibly taken) when the pool
 // has nothing of this size: the caller then allocates and zeroes as usual.

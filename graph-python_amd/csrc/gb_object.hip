@@ -124,30 +124,19 @@ void gb_drop_transpose(GB_Obj *A) {
     A->t_colidx = nullptr;
     A->t_vals = nullptr;
     A->t_valid = false;
-    for (int o = 0; o < 2; o++) {
-        gb_free(A->hub_tab[o]);
-        A->hub_tab[o] = nullptr;
-        A->hub_n[o] = A->hub_H[o] = 0;
-        A->maxdeg[o] = 0;
-        gb_free(A->rows_ne[o]);
-        A->rows_ne[o] = nullptr;
-        gb_free(A->phead[o]);
-        gb_free(A->pdeg[o]);
-        A->phead[o] = nullptr;
-        A->pdeg[o] = nullptr;
-        gb_free(A->long_tab[o]);
-        A->long_tab[o] = nullptr;
-        gb_free(A->hot_ci[o]);
-        gb_free(A->hot_cols[o]);
-        A->hot_ci[o] = nullptr;
-        A->hot_cols[o] = nullptr;
-        A->hot_n[o] = 0;
-        A->long_n[o] = 0;
-        gb_free(A->nar_vx[o]);
-        A->nar_vx[o] = nullptr;
-        A->nar_k[o] = 0;
-        A->nar_done[o] = false;
-    }
+    for (gb_orient_cache &c : A->oc) gb_orient_cache_drop(c);
+}
+
+void gb_orient_cache_drop(gb_orient_cache &c) {
+    gb_free(c.hub_tab);
+    gb_free(c.rows_ne);
+    gb_free(c.phead);
+    gb_free(c.pdeg);
+    gb_free(c.long_tab);
+    gb_free(c.hot_ci);
+    gb_free(c.hot_cols);
+    gb_free(c.nar_vx);
+    c = gb_orient_cache{};
 }
 
 void gb_obj_free_storage(GB_Obj *A) {

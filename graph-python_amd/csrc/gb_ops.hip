@@ -67,7 +67,7 @@ static void spmv_build_views(spmv_views &V, GB_Obj *mask, GrB_Semiring sr, GB_Ob
     if (V.m.bits && mask && mask->kind != GB_KIND_MATRIX && mask->nvals_valid && mask->nvals == 0) V.m.h_count = 0;
     // the fused assign's target is the mask (take_pending_assign): its count before this call's
     // assign, as the host knew it when the assign was deferred (a BFS's first level after
-    // clearing v: 0), lets gb_spmv pick push on the host without the prep launch
+    // clearing v: 0), lets gb_spmv_iso pick push on the host without the prep launch
     // -- a stored-entry count equals the set-bit count only for a structural mask; for a value
     // mask it is an upper bound, which still bounds the open rows of a complemented mask from
     // below but says nothing for a plain one

@@ -706,7 +706,7 @@ void gb_view_hot(gb_csr_view &v, GB_Obj *A, int orient) {
     int64_t H = gb_knob("xhot_cols");
     if (H <= 0) H = 1LL << 18;  // 2 MB of fp64 x (tools/xhot_probe.py, s22: 2^16 684 us, 2^18 662, 2^19 667, 2^20 677)
     if (H > v.ncols) H = v.ncols;
-    if (!A->hot_ci[orient]) {
+    if (!A->oc[orient].hot_ci) {
         // worth it only when x does not fit the L2 anyway and there is enough to gather
         if (knob != 2 && (v.nvals < (1LL << 22) || v.ncols <= 2 * H)) return;
         if (H <= 0 || v.nvals == 0) return;
@@ -739,13 +739,13 @@ void gb_view_hot(gb_csr_view &v, GB_Obj *A, int orient) {
         int32_t *hci = gb_malloc_n<int32_t>(v.nvals);
         hipLaunchKernelGGL(k_hot_remap, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), v.colidx, v.nvals, rank, hci);
         GB_LAUNCH_CHECK();
-        A->hot_ci[orient] = hci;
-        A->hot_cols[orient] = hot;
-        A->hot_n[orient] = H;
+        A->oc[orient].hot_ci = hci;
+        A->oc[orient].hot_cols = hot;
+        A->oc[orient].hot_n = H;
     }
-    v.hcolidx = A->hot_ci[orient];
-    v.hcols = A->hot_cols[orient];
-    v.nhot = A->hot_n[orient];
+    v.hcolidx = A->oc[orient].hot_ci;
+    v.hcols = A->oc[orient].hot_cols;
+    v.nhot = A->oc[orient].hot_n;
 }
 
 // ------------------------------------------------------------------ narrow values
@@ -799,7 +799,7 @@ void gb_view_narrow(gb_csr_view &v, GB_Obj *A, int orient) {
     const bool sgn = code == GBAMD_T_INT16 || code == GBAMD_T_INT32 || code == GBAMD_T_INT64;
     const bool uns = code == GBAMD_T_UINT16 || code == GBAMD_T_UINT32 || code == GBAMD_T_UINT64;
     if (!sgn && !uns) return;
-    if (!A->nar_done[orient]) {
+    if (!A->oc[orient].nar_done) {
         const size_t ts = gb_type_size(code);
         gb_scratch s;
         long long *st = s.get<long long>(3);
@@ -860,10 +860,10 @@ void gb_view_narrow(gb_csr_view &v, GB_Obj *A, int orient) {
             });
             GB_LAUNCH_CHECK();
         }
-        A->nar_vx[orient] = nv;
-        A->nar_k[orient] = k;
-        A->nar_done[orient] = true;
+        A->oc[orient].nar_vx = nv;
+        A->oc[orient].nar_k = k;
+        A->oc[orient].nar_done = true;
     }
-    v.nvx = A->nar_vx[orient];
-    v.nvk = A->nar_vx[orient] ? A->nar_k[orient] : 0;
+    v.nvx = A->oc[orient].nar_vx;
+    v.nvk = A->oc[orient].nar_vx ? A->oc[orient].nar_k : 0;
 }

@@ -1,4 +1,4 @@
-"""Open rows packed across a wave's steps in the iso SpMV's pull and push (csrc/gb_mxv.hip,
+"""Open rows packed across a wave's steps in the iso SpMV's pull and push (csrc/gb_spmv_iso.hip,
 knob iso_pack: 0 both on -- the default --, 1 both off: the per-step loops, 2 pull only, 3 push
 only).  The packed pull takes a wave's words in groups of 4 steps (16 words, one lane each),
 packs the open rows by a prefix sum of the words' popcounts and runs its chain of reads once per

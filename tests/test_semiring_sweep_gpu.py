@@ -391,15 +391,10 @@ ISO = [("max", "minus", "INT16", 5, -3, "both"), ("min", "div", "FP64", 3.0, -0.
 IDEMPOTENT = {"any", "min", "max", "lor", "land", "bor", "band"}
 
 
-@pytest.mark.parametrize("n", [300, 5000])
-@pytest.mark.parametrize("case", ISO, ids=lambda c: f"{c[0]}_{c[1]}-{c[2]}-{c[5]}")
-def test_iso_operands_spmv(gb, case, n):
-    """A and u built from a scalar: an idempotent monoid gives an iso result (the BFS kernel,
-    k_iso_work, with the one value from gb_iso_eval), in every direction, for a one-entry and a
-    dense u; FIRST / SECOND need only the operand they read to be iso, also under the vxm swap.
-    A non-idempotent monoid must not come out iso: its values are counts and parities."""
+def _iso_spmv_operands(gb, case, n):
+    """The operands of one ISO case on the n x (n + 13) pattern with one long row: yields
+    (kind, fill, Ag, ug, expected) for mxv and vxm with a one-entry and a dense u."""
     mon, mul, dt, a, b, which = case
-    sr, zt = lookup(gb, mon, mul, dt)
     rng = sc.rng_of("iso", case, n)
     m = n + 13
     p = rng.random((n, m)) < 8.0 / n
@@ -411,7 +406,6 @@ def test_iso_operands_spmv(gb, case, n):
         noise_A[p] = sc.draw(dt, rng, int(p.sum()))
         noise_A = p, noise_A
         A_var_g = to_gb(gb, noise_A)
-    want_iso = mon in IDEMPOTENT
     for fill in ("one", "dense"):
         for kind in ("mxv", "vxm"):
             size = m if kind == "mxv" else n
@@ -435,12 +429,51 @@ def test_iso_operands_spmv(gb, case, n):
                 e = expect(mon, mul, dt, dm.mxv, Am, Um)
             else:
                 e = expect(mon, mul, dt, dm.vxm, Um, Am)
-            for direction in (0, 1, 2):
-                with _knobs(gb, spmv_direction=direction):
-                    w = (Ag.mxv(ug, sr) if kind == "mxv" else ug.vxm(Ag, sr)).new()
-                what = f"{mon}_{mul}[{dt}] n={n} {kind} u={fill} direction={direction}"
-                check_T(w, e, zt, mon, what)
-                assert is_iso(w) == want_iso, f"{what}: iso {is_iso(w)}, expected {want_iso}"
+            yield kind, fill, Ag, ug, e
+
+
+@pytest.mark.parametrize("n", [300, 5000])
+@pytest.mark.parametrize("case", ISO, ids=lambda c: f"{c[0]}_{c[1]}-{c[2]}-{c[5]}")
+def test_iso_operands_spmv(gb, case, n):
+    """A and u built from a scalar: an idempotent monoid gives an iso result (the BFS kernel,
+    k_iso_work, with the one value from gb_iso_eval), in every direction, for a one-entry and a
+    dense u; FIRST / SECOND need only the operand they read to be iso, also under the vxm swap.
+    A non-idempotent monoid must not come out iso: its values are counts and parities."""
+    mon, mul, dt = case[:3]
+    sr, zt = lookup(gb, mon, mul, dt)
+    want_iso = mon in IDEMPOTENT
+    for kind, fill, Ag, ug, e in _iso_spmv_operands(gb, case, n):
+        for direction in (0, 1, 2):
+            with _knobs(gb, spmv_direction=direction):
+                w = (Ag.mxv(ug, sr) if kind == "mxv" else ug.vxm(Ag, sr)).new()
+            what = f"{mon}_{mul}[{dt}] n={n} {kind} u={fill} direction={direction}"
+            check_T(w, e, zt, mon, what)
+            assert is_iso(w) == want_iso, f"{what}: iso {is_iso(w)}, expected {want_iso}"
+
+
+# z is bool and x is not; z = x, not bool; only the operand that is read is iso
+ISO_LAUNCH = [c for c in ISO if c[:3] in {("land", "gt", "INT32"), ("max", "minus", "INT16"), ("min", "first", "UINT64")}]
+
+
+@pytest.mark.parametrize("case", ISO_LAUNCH, ids=lambda c: f"{c[0]}_{c[1]}-{c[2]}-{c[5]}")
+def test_iso_value_in_every_launch_shape(gb, case):
+    """The iso value has one writer, gb_iso_eval in k_iso_work, whatever launches the call
+    makes: with and without the prep launch (host_dir 1 forces it when nothing is known about
+    the frontier), in every direction, with the packed finish (value written up front) and the
+    unpacked one (iso_packed 1: written late, by the finishing block)."""
+    mon, mul, dt = case[:3]
+    assert len(ISO_LAUNCH) == 3
+    sr, zt = lookup(gb, mon, mul, dt)
+    for kind, fill, Ag, ug, e in _iso_spmv_operands(gb, case, 300):
+        for direction in (0, 1, 2):
+            for host_dir in (0, 1):
+                for iso_packed in (0, 1):
+                    with _knobs(gb, spmv_direction=direction, host_dir=host_dir, iso_packed=iso_packed):
+                        w = (Ag.mxv(ug, sr) if kind == "mxv" else ug.vxm(Ag, sr)).new()
+                    what = (f"{mon}_{mul}[{dt}] {kind} u={fill} direction={direction} host_dir={host_dir} "
+                            f"iso_packed={iso_packed}")
+                    check_T(w, e, zt, mon, what)
+                    assert is_iso(w), f"{what}: not iso"
 
 
 @pytest.mark.parametrize("case", ISO, ids=lambda c: f"{c[0]}_{c[1]}-{c[2]}-{c[5]}")

@@ -1,6 +1,6 @@
 """Kernel gaps of the bench's level BFS without a profiler: the library stamps each k_iso_work
 launch's start and end on the device wall clock (s_memrealtime, 100 MHz) when
-GRAPHBLAS_AMD_ISO_TS names a dump file (csrc/gb_mxv.hip iso_ts_mark).  Runs bench.py's timed
+GRAPHBLAS_AMD_ISO_TS names a dump file (csrc/gb_spmv_iso.hip iso_ts_mark).  Runs bench.py's timed
 loop shape (16 seeded roots on R-MAT s22, any_pair, warm-up first) and prints, per BFS, the
 launches, the summed launch durations and the summed idle gaps between them, then the
 averages.  Diagnostic only (tools/)."""
