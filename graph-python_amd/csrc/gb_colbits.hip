@@ -957,16 +957,7 @@ bool gb_colbits_assign_scalar(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, const vo
     const int vs = (int)C->type->size;
     if ((double)k * (double)n * vs > 64e9) return false;
     unsigned long long xv = 0;
-    gb_with_type(C->type->code, [&](auto z) {
-        using D = decltype(z);
-        gb_with_type(xcode, [&](auto y) {
-            using S = decltype(y);
-            S s;
-            memcpy(&s, x, sizeof(S));
-            D dv = gb_cast<D, S>(s);
-            memcpy(&xv, &dv, sizeof(D));
-        });
-    });
+    gb_cast_scalar(&xv, C->type->code, x, xcode);
     if (!M->cw) to_cw(M, nullptr, 0, nullptr);
     if (!C->cw) to_cw(C, nullptr, 0, nullptr);
     cw_expand(C);

@@ -509,15 +509,8 @@ GrB_Info GxB_Global_set_int(const char *key, int64_t value) {
 
 GrB_Info GxB_Global_get_int(const char *key, int64_t *value) {
     if (!key || !value) return GrB_NULL_POINTER;
-    // statistics (read-only): BFS level speculation (gb_ops.hip)
-    if (!strcmp(key, "stat_bfs_spec_adopted")) {
-        *value = g_stat_spec_adopted.load(std::memory_order_relaxed);
-        return GrB_SUCCESS;
-    }
-    if (!strcmp(key, "stat_bfs_spec_rollbacks")) {
-        *value = g_stat_spec_rollbacks.load(std::memory_order_relaxed);
-        return GrB_SUCCESS;
-    }
+    // statistics (read-only): BFS level speculation (gb_bfs_loop.hip)
+    if (gb_deferred_stat(key, value)) return GrB_SUCCESS;
     // vector counts read with a device copy (stream sync) instead of the kernel's mailbox
     if (!strcmp(key, "stat_spmv_host_push")) {
         *value = g_stat_host_push.load(std::memory_order_relaxed);

@@ -22,6 +22,20 @@ static void gb_with_type(int code, F &&f) {
     }
 }
 
+// cast the host scalar *x of type xcode to type ct into *out (at most 8 bytes are written)
+static void gb_cast_scalar(void *out, int ct, const void *x, int xcode) {
+    gb_with_type(ct, [&](auto z) {
+        using D = decltype(z);
+        gb_with_type(xcode, [&](auto y) {
+            using S = decltype(y);
+            S sv;
+            memcpy(&sv, x, sizeof(S));
+            D dv = gb_cast<D, S>(sv);
+            memcpy(out, &dv, sizeof(D));
+        });
+    });
+}
+
 struct gb_sr_info {
     int mon, mul;
     int xcode;        // multiplier input type (== zcode for positional ops)

@@ -178,45 +178,43 @@ void gb_hip_check(hipError_t e, const char *what);
 #define GB_HIP(x) gb_hip_check((x), #x)
 #define GB_LAUNCH_CHECK() gb_hip_check(hipGetLastError(), "kernel launch")
 
-// API-boundary wrapper: runs body, converts exceptions to GrB_Info and stores
-// the message on the error object (reference core/exceptions.py:124-155 reads
-// it back with GrB_<Type>_error on the call's output argument).
-// a deferred assign (gb_asg, gb_ops.hip) is carried out before any API call
-// other than the SpMV that may fuse it
-extern std::atomic<bool> g_pending_active;
-void gb_pending_flush();
-// a speculatively enqueued next BFS level (gb_ops.hip): rolled back before any API call that
-// could observe it, unless the caller resolves it itself (g_spec_hold > 0); gb_spec_resolve(obj)
-// leaves it in place when obj is a read-only target the speculation does not touch
-extern std::atomic<bool> g_spec_active;
-extern thread_local int g_spec_hold;
-void gb_spec_resolve(const void *keep);
-extern std::atomic<int64_t> g_stat_spec_adopted, g_stat_spec_rollbacks;  // GxB_Global_get_int("stat_...")
 extern std::atomic<int64_t> g_stat_nvals_copy;
 extern std::atomic<int64_t> g_stat_host_push;  // SpMV launches whose push direction the host proved
 // named counters of which kernel classes a call used (host-side, off the per-level BFS path):
 // GxB_Global_get_int("stat_<name>") reads them; tests assert that a workload reached a class
 void gb_stat_add(const char *name, int64_t v);
 bool gb_stat_get(const char *name, int64_t *v);
-struct gb_spec_hold_guard {
-    gb_spec_hold_guard() { g_spec_hold++; }
-    ~gb_spec_hold_guard() { g_spec_hold--; }
-};
-// A pending root (gb_object.hip): `GrB_Vector_setElement_BOOL(q, true, i)` on an empty BOOL vector
-// -- the BFS start, notebooks/Example B.1 cell 8 -- is recorded instead of launched; the level
-// SpMV of the notebook shape that reads q consumes it (its kernel pushes from vertex i, gb_spmv_iso.hip
-// gb_push_root), and the deferred stamp `v<q> = 1` before it keeps it pending (g_root_hold); any
-// other API call materialises it first (gb_root_flush: the single-thread set launch it replaced).
-extern std::atomic<bool> g_root_active;
-extern thread_local int g_root_hold;
-void gb_root_flush();
-bool gb_root_pending(const GB_Obj *v);
-int64_t gb_root_take(GB_Obj *v);  // the root index, the record cleared; -1 when v holds none
-const void *gb_bool_true_dev();   // one device byte holding true (a consumed root's iso value)
-struct gb_root_hold_guard {
-    gb_root_hold_guard() { g_root_hold++; }
-    ~gb_root_hold_guard() { g_root_hold--; }
-};
+
+// ------------------------------------------------------------------ deferred work (gb_bfs_loop.hip)
+// The level-BFS loop's host side defers three things -- a speculatively enqueued next level, a
+// pending root (`q[src] = true` on an empty BOOL vector) and a deferred stamp (`v<q> = d`, fused
+// into the next SpMV: gb_asg below) -- and no call may observe any of them.  This block is the
+// whole contract between that file and the rest of the library.
+struct gb_desc;
+enum : unsigned { GB_DEFER_SPEC = 1, GB_DEFER_ROOT = 2, GB_DEFER_STAMP = 4, GB_DEFER_ALL = 7 };
+extern std::atomic<unsigned> g_deferred;  // a bit per mechanism with something live: 0 outside a BFS loop
+// carry out or undo what is live, in the one right order, except the mechanisms in `keep`;
+// reader: an object the caller only counts (a speculation stays unless that is its stamp target)
+void gb_deferred_resolve(unsigned keep, const void *reader);
+// GrB_Vector_setElement_BOOL(v, true, i): true when recorded as the pending root instead
+bool gb_root_try_defer(GB_Obj *v, int64_t i);
+// w<mask>(:) = x without accum (xc: x as w's type): true when recorded as the deferred stamp;
+// a pending root survives the call only as that stamp's mask
+bool gb_stamp_try_defer(GB_Obj *w, GB_Obj *mask, const char *xc, const gb_desc &d);
+// GrB_Vector_assign_<T>: true when the call is over with *info -- it was the stamp a
+// speculation predicted and already carried out (absorbed), or matching it failed
+bool gb_deferred_absorb_assign(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const void *x, int xcode,
+                               const GrB_Index *I, GrB_Index ni, GrB_Descriptor desc, GrB_Info *info);
+bool gb_deferred_stat(const char *key, int64_t *value);  // "stat_bfs_spec_adopted" / "stat_bfs_spec_rollbacks"
+// GrB_mxv / GrB_vxm (and the row reduction of gb_ops.hip): adopts, fuses or resolves what is live
+void gb_do_spmv(GB_Obj *w, GB_Obj *mask, GrB_BinaryOp accum, GrB_Semiring sr, GB_Obj *A, GB_Obj *u, const gb_desc &d,
+                bool vxm);
+// what that file calls back: the assigns of gb_ops.hip, the one-thread set launch of gb_object.hip
+void gb_make_values_writable(GB_Obj *w);
+bool gb_assign_all_scalar_fast(GB_Obj *w, GB_Obj *mask, const char *xc, const gb_desc &d);
+void gb_vector_assign_scalar(GB_Obj *w, GB_Obj *mask, GrB_BinaryOp accum, const void *x, int xcode,
+                             const GrB_Index *I, int64_t ni, const gb_desc &d);
+void gb_vec_set_true(GB_Obj *v, int64_t i);
 
 // roctx ranges named by the API entry point around each library call (environment
 // GRAPHBLAS_AMD_ROCTX=1; the roctx library is loaded then, never otherwise), so a rocprofv3
@@ -235,13 +233,17 @@ struct gb_roctx_range {
     }
 };
 
-template <bool FLUSH = true, class F>
-GrB_Info gb_api_impl(GB_Obj *errobj, F &&body, const char *name = nullptr) {
+// API-boundary wrapper: runs body, converts exceptions to GrB_Info and stores
+// the message on the error object (reference core/exceptions.py:124-155 reads
+// it back with GrB_<Type>_error on the call's output argument).
+// Deferred work other than KEEP's is resolved first (reader: see gb_deferred_resolve); when none
+// is live, which is every call outside a BFS loop, that is one load and one branch.
+template <unsigned KEEP = 0, class F>
+GrB_Info gb_api_impl(GB_Obj *errobj, F &&body, const char *name = nullptr, const void *reader = nullptr) {
     gb_roctx_range range(name);
     try {
-        if (FLUSH && !g_spec_hold && g_spec_active.load(std::memory_order_acquire)) gb_spec_resolve(nullptr);
-        if (FLUSH && !g_root_hold && g_root_active.load(std::memory_order_acquire)) gb_root_flush();
-        if (FLUSH && g_pending_active.load(std::memory_order_acquire)) gb_pending_flush();
+        if (KEEP != GB_DEFER_ALL && (g_deferred.load(std::memory_order_acquire) & ~KEEP) != 0)
+            gb_deferred_resolve(KEEP, reader);
         body();
         if (errobj && errobj->magic == GB_MAGIC) errobj->err.clear();
         return GrB_SUCCESS;
@@ -255,18 +257,8 @@ GrB_Info gb_api_impl(GB_Obj *errobj, F &&body, const char *name = nullptr) {
         return GrB_PANIC;
     }
 }
-template <class F>
-GrB_Info gb_api_named(const char *name, GB_Obj *errobj, F &&body) {
-    return gb_api_impl<true>(errobj, std::forward<F>(body), name);
-}
-// GrB_mxv / GrB_vxm: the deferred assign is fused or flushed inside (do_spmv)
-template <class F>
-GrB_Info gb_api_keep_pending_named(const char *name, GB_Obj *errobj, F &&body) {
-    return gb_api_impl<false>(errobj, std::forward<F>(body), name);
-}
 // the entry point's own name (__func__) names its trace range
-#define gb_api(obj, ...) gb_api_named(__func__, obj, __VA_ARGS__)
-#define gb_api_keep_pending(obj, ...) gb_api_keep_pending_named(__func__, obj, __VA_ARGS__)
+#define gb_api(obj, ...) gb_api_impl(obj, __VA_ARGS__, __func__)
 
 // ------------------------------------------------------------------ host-time probes
 // Diagnostics of the per-call host path (environment GRAPHBLAS_AMD_HPROF=1): cumulative
@@ -471,6 +463,18 @@ struct gb_desc {
     bool replace = false, comp = false, structure = false, tran0 = false, tran1 = false;
 };
 gb_desc gb_read_desc(const GrB_Descriptor d);
+inline void gb_check_semiring(GrB_Semiring sr) {
+    GB_REQUIRE(sr, GrB_NULL_POINTER, "semiring is NULL");
+    GB_REQUIRE(sr->magic == GB_MAGIC, GrB_UNINITIALIZED_OBJECT, "invalid semiring");
+}
+inline void gb_check_binop(GrB_BinaryOp op, bool allow_null) {
+    if (!op) {
+        GB_REQUIRE(allow_null, GrB_NULL_POINTER, "operator is NULL");
+        return;
+    }
+    GB_REQUIRE(op->magic == GB_MAGIC, GrB_UNINITIALIZED_OBJECT, "invalid operator");
+}
+inline int64_t gb_ncols_of(const GB_Obj *A) { return A->kind == GB_KIND_MATRIX ? A->ncols : 1; }
 // batched-frontier fast paths (gb_colbits.hip): C<M> = A lor.land B with A of at most 64
 // rows, and C<M> = x over all indices; false when the call is not of that shape (the
 // caller then runs the general path on CSR operands)
@@ -541,8 +545,8 @@ void gb_writeback_matrix(GB_Obj *C, gb_mat_result &T, GB_Obj *M, const gb_desc &
 // A deferred `w<q>(:) = x` (GrB_Vector_assign with a value or structural mask q,
 // no accum / replace, all indices) carried out by the iso SpMV kernel whose input
 // is q and whose mask is w's structure (the BFS level loop: v<q> = d;
-// q<!v.S> = q lor.land A).  gb_ops.hip defers such assigns; every other API call
-// performs them first (gb_pending_flush, called by gb_api).
+// q<!v.S> = q lor.land A).  gb_bfs_loop.hip defers such assigns; every other API call
+// performs them first (gb_deferred_resolve, called by gb_api).
 struct gb_asg {
     uint64_t *bits = nullptr;  // w's bitmap (read as the call's mask, OR q)
     void *vals = nullptr;      // w's dense values
@@ -555,7 +559,7 @@ struct gb_asg {
     // u's device count is exact (written by the kernel that produced u, earlier on the stream):
     // an empty u ends the launch early (the speculated level after a BFS's last one)
     bool u_count_exact = false;
-    // u is a pending root (gb_root_take): the frontier is {root}; u's storage does not hold it
+    // u is a pending root (gb_bfs_loop.hip): the frontier is {root}; u's storage does not hold it
     int64_t root = -1;
 };
 void gb_spmv(gb_vec_result &T, const gb_csr_view &A, const gb_csr_view *Apush, gb_bitmap_view &u,

@@ -409,7 +409,7 @@ __device__ __forceinline__ long long gb_push_phase(int64_t nwords_u, const uint6
     return added;
 }
 
-// Push from a single pending vertex (the BFS root, gb_internal.h g_root_active): the host knows
+// Push from a single pending vertex (the BFS root, gb_bfs_loop.hip gb_root_try_defer): the host knows
 // the frontier is {root}, so the kernel neither tests the hub table against the frontier nor
 // scans its bitmap words (which do not hold the root) -- the root's edges are spread over the
 // whole grid, 4 per lane per step, and block 0 carries out the fused stamp v<q> = x for it.

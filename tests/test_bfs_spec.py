@@ -1,4 +1,4 @@
-"""BFS level speculation (csrc/gb_ops.hip, knob bfs_spec): after a level of the notebook loop
+"""BFS level speculation (csrc/gb_bfs_loop.hip, knob bfs_spec): after a level of the notebook loop
 (reference notebooks/Example B.1 -- Level BFS.ipynb cell 8: `v<q.V> = d; q<!v.S,replace> = q
 (+).(x) A`) the library enqueues the next level behind it and installs that result when the host
 issues exactly the predicted stamp and SpMV; anything else rolls it back first.  These tests drive
@@ -483,3 +483,96 @@ def test_pending_root_is_unobservable(gb, graph):
     assert on["level1_consumed"] == off["level1_consumed"] == expect
     assert on["v6"] == off["v6"] == 1
     assert on["root_pushes"] >= 1 and off["root_pushes"] == 0
+
+
+# ---- two mechanisms live at once: (a) root pending + stamp deferred, before the first SpMV;
+# (b) speculation active + stamp absorbed, from level 2 on.  One observer call is put into each
+# moment and everything it and the loop then produce is compared exactly with the same calls
+# under fuse_assign = bfs_spec = root_defer = 1 (nothing deferred).
+HUB_N, HUB = 130, 64  # three bitmap words, the last one partial; the hub on a word boundary
+
+
+def hub_path_graph(gb):
+    """the path 0-1-...-129 plus a hub joined to 70 vertices (63 and 65, its path neighbours, among them)"""
+    nb = list(range(3, HUB_N, 2)) + [10, 20, 40, 80, 120, 128]
+    assert len(set(nb)) == 70 and HUB not in nb
+    und = {(i, i + 1) for i in range(HUB_N - 1)} | {(HUB, j) for j in nb}
+    e = np.array(sorted(und | {(j, i) for i, j in und}))
+    return gb.Matrix.from_coo(e[:, 0], e[:, 1], True, nrows=HUB_N, ncols=HUB_N)
+
+
+def obs_extract_v(lib, q, v, other, src):
+    out = []
+    for i in (src, 1, 2, HUB, HUB_N - 1):
+        x = ctypes.c_int32(-1)
+        out.append((lib.GrB_Vector_extractElement_INT32(ctypes.byref(x), v._carg, i), x.value))
+    return out
+
+
+def obs_set_v(lib, q, v, other, src):
+    return lib.GrB_Vector_setElement_INT32(v._carg, 77, HUB_N - 1)
+
+
+OBSERVERS = {  # name: (the call, whether it touches v)
+    "nvals_v": (lambda lib, q, v, other, src: v.nvals, True),
+    "nvals_q": (lambda lib, q, v, other, src: q.nvals, False),
+    "extract_v": (obs_extract_v, True),
+    "dup_q": (lambda lib, q, v, other, src: [a.tolist() for a in q.dup().to_coo()], False),
+    "clear_other": (lambda lib, q, v, other, src: (other.clear(), other.nvals), False),
+    "set_v": (obs_set_v, True),
+    "wait_v": (lambda lib, q, v, other, src: (v.wait(), "waited"), True),
+}
+
+
+def run_observed(gb, A, src, moment, observer):
+    """the notebook loop from src with the observer between the stamp and the SpMV of level 1
+    (moment a) or 3 (moment b); returns what a caller can see of it, and the counter deltas"""
+    lib, n = gb.lib, HUB_N
+    q, v = gb.Vector(bool, n), gb.Vector(gb.INT32, n)
+    other = gb.Vector.from_coo([1, 70, 129], [3, 4, 5], dtype=gb.INT64, size=n)
+    ok(lib.GrB_Vector_setElement_BOOL(q._carg, True, src))
+    levels, seen, rolled, adopted = [], None, None, None
+    nv = U64()
+    for d in range(1, n + 2):
+        ok(lib.GrB_Vector_assign_INT32(v._carg, q._carg, None, d, lib.GrB_ALL, n, None), "stamp")
+        here = d == (1 if moment == "a" else 3)
+        if here:
+            r0 = stat(gb, "stat_bfs_spec_rollbacks")
+            seen = observer(lib, q, v, other, src)
+            rolled = stat(gb, "stat_bfs_spec_rollbacks") - r0
+            a0 = stat(gb, "stat_bfs_spec_adopted")
+        ok(lib.GrB_vxm(q._carg, v._carg, None, lib.GxB_ANY_PAIR_BOOL, q._carg, A._carg, lib.GrB_DESC_RSC), "vxm")
+        if here:
+            adopted = stat(gb, "stat_bfs_spec_adopted") - a0
+        ok(lib.GrB_Vector_nvals(ctypes.byref(nv), q._carg), "nvals q")
+        levels.append(nv.value)
+        if nv.value == 0:
+            break
+    assert seen is not None, "the loop ended before the observer's level"
+    visible = (levels, [a.tolist() for a in v.to_coo()], [a.tolist() for a in q.to_coo()], seen)
+    return visible, rolled, adopted
+
+
+@pytest.mark.parametrize("name", list(OBSERVERS))
+def test_all_deferrals_at_once(gb, name):
+    A = hub_path_graph(gb)
+    observer, touches_v = OBSERVERS[name]
+    knobs = ("fuse_assign", "bfs_spec", "root_defer")
+    for src in (0, HUB):
+        for moment in ("a", "b"):
+            on, rolled, adopted = run_observed(gb, A, src, moment, observer)
+            for k in knobs:
+                gb.set_knob(k, 1)
+            try:
+                off, rolled_off, adopted_off = run_observed(gb, A, src, moment, observer)
+            finally:
+                for k in knobs:
+                    gb.set_knob(k, 0)
+            assert on == off, (name, src, moment)
+            assert rolled_off == 0 and adopted_off == 0
+            assert len(on[0]) >= 4 and on[0][-1] == 0
+            if moment == "b" and touches_v:
+                assert rolled >= 1, "the observer saw v without the speculation rolled back"
+            if moment == "b" and name == "nvals_q":
+                # a count of q leaves the speculation in place: the SpMV after it adopts it
+                assert rolled == 0 and adopted == 1
