@@ -523,6 +523,13 @@ GrB_Info GxB_Global_get_int(const char *key, int64_t *value) {
     if (!strcmp(key, "iso_ts_dump")) {  // diagnostics: GRAPHBLAS_AMD_ISO_TS (gb_spmv_iso.hip)
         return gb_api(nullptr, [&] { *value = gb_iso_ts_dump(); });
     }
+    // the sort's per-class row counts (read from the device here, not by the sort) and the
+    // defaults of its class bounds (gb_sort.hip)
+    {
+        bool mine = false;
+        const GrB_Info info = gb_api(nullptr, [&] { mine = gb_sort_stat(key, value); });
+        if (mine || info != GrB_SUCCESS) return info;
+    }
     // named kernel-class counters (gb_stat_add): "stat_" + name; 0 before the first count
     if (!strncmp(key, "stat_", 5)) {
         if (!gb_stat_get(key + 5, value)) *value = 0;

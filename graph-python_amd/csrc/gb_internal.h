@@ -590,6 +590,11 @@ void gb_select(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_IndexUnaryOp op, GB
 void gb_kronecker(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_BinaryOp binop, GB_Obj *A, GB_Obj *B,
                   const gb_desc &d);
 
+// sort (gb_sort.hip): the entry points are GxB_Matrix_sort / GxB_Vector_sort; GxB_Global_get_int
+// asks here for "stat_sort_rows_{wave,block,long}" (rows each class took in the last matrix sort,
+// read from the device) and for the defaults of "sort_wave_max" / "sort_block_max"
+bool gb_sort_stat(const char *key, int64_t *value);
+
 // hash Gustavson C = A*B (gb_spgemm_hash.hip): flops = per-row product counts
 void gb_spgemm_hash(gb_mat_result &T, gb_csr_view &A, gb_csr_view &B, GrB_Semiring sr, bool iso,
                     const void *av, const void *bv, const int64_t *flops);

@@ -1,4 +1,4 @@
-"""``Vector.ss`` / ``Matrix.ss`` extension namespaces: the prefix scan.
+"""``Vector.ss`` / ``Matrix.ss`` extension namespaces: the prefix scan and sort.
 
 ``prefix_scan`` restates reference core/ss/prefix_scan.py:12-172: a
 Blelloch up-sweep / down-sweep expressed entirely as masked, accumulated
@@ -9,13 +9,19 @@ so the scan runs on the device kernels of the hot path (masked SpGEMM /
 SpMV + accumulate write-back).  Compaction / de-compaction of the index
 space goes through to_coo / from_coo (the reference uses the ss export /
 import of the same arrays).
+
+``sort`` is one call of GxB_Matrix_sort / GxB_Vector_sort (csrc/gb_sort.hip): a
+segmented sort on the device, nothing goes through the host.  The k largest
+entries of every row are ``C, P = A.ss.sort(">")`` followed by
+``C.select("col<=", k - 1)`` (and the same select of ``P`` for where they came from).
 """
 from math import ceil, log2
 
 import numpy as np
 
 from . import operator as _op
-from .dtypes import INT8
+from .base import call, descriptor_lookup
+from .dtypes import INT8, UINT64
 
 
 def _scan_monoid(x, op):
@@ -127,6 +133,22 @@ _ORDERS = {"rowwise": "rowwise", "row": "rowwise", "rows": "rowwise", "c": "roww
            "columns": "columnwise", "f": "columnwise"}
 
 
+def _sort_op(parent, op):
+    """The typed BinaryOp of a sort (reference core/ss/matrix.py:4029-4033): a Monoid gives its
+    binary operator; whether it is an order is the library's decision."""
+    t = _op.get_typed_op(op, parent.dtype, kind="binary")
+    if t.opclass == "Monoid":
+        t = t.binaryop[t.type]
+    if t.opclass != "BinaryOp":
+        raise TypeError(f"Bad type for argument `op` in sort: expected BinaryOp, got {t.opclass}")
+    return t
+
+
+def _sort_opts(opts):
+    opts.pop("nthreads", None)  # accepted as in the reference; the device has no thread count
+    return opts
+
+
 class VectorSS:
     def __init__(self, parent):
         self._parent = parent
@@ -134,6 +156,22 @@ class VectorSS:
     def scan(self, op=None, *, name=None):
         """Prefix scan with a monoid (reference core/ss/vector.py:1365-1375)."""
         return prefix_scan(self._parent, _op.monoid.plus if op is None else op, name=name)
+
+    def sort(self, op=_op.binary.lt, *, values=True, permutation=True, **opts):
+        """GxB_Vector_sort (reference core/ss/vector.py:1562-1617): ``(w, p)``, the values in
+        the order of ``op`` (ties by ascending index) at positions 0 .. nvals-1 and the indices
+        they came from; an output that was not requested is ``None``."""
+        from .vector import Vector
+
+        parent = self._parent
+        op = _sort_op(parent, op)
+        desc = descriptor_lookup(**_sort_opts(opts))
+        if not values and not permutation:
+            return None, None
+        w = Vector(parent.dtype, parent.size, name="Values") if values else None
+        p = Vector(UINT64, parent.size, name="Permutation") if permutation else None
+        call("GxB_Vector_sort", [w, p, op, parent, desc])
+        return w, p
 
 
 class MatrixSS:
@@ -149,3 +187,23 @@ class MatrixSS:
         if _ORDERS[key] == "columnwise":
             parent = parent.T
         return prefix_scan(parent, _op.monoid.plus if op is None else op, name=name)
+
+    def sort(self, op=_op.binary.lt, order="rowwise", *, values=True, permutation=True, **opts):
+        """GxB_Matrix_sort (reference core/ss/matrix.py:3991-4055): ``(C, P)``, the values of
+        every row (column, if columnwise) in the order of ``op`` (ties by ascending index) moved
+        to the left (top), and the column (row) indices they came from; both have the parent's
+        shape, an output that was not requested is ``None``."""
+        from .matrix import Matrix
+
+        key = order.lower() if isinstance(order, str) else order
+        if key not in _ORDERS:
+            raise ValueError(f"Bad value for order: {order!r}")
+        parent = self._parent
+        op = _sort_op(parent, op)
+        desc = descriptor_lookup(transpose_first=_ORDERS[key] == "columnwise", **_sort_opts(opts))
+        if not values and not permutation:
+            return None, None
+        C = Matrix(parent.dtype, parent.nrows, parent.ncols, name="Values") if values else None
+        P = Matrix(UINT64, parent.nrows, parent.ncols, name="Permutation") if permutation else None
+        call("GxB_Matrix_sort", [C, P, op, parent, desc])
+        return C, P

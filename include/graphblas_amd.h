@@ -331,6 +331,18 @@ GrB_Info GrB_Matrix_kronecker_Monoid(GrB_Matrix C, const GrB_Matrix Mask, const 
 GrB_Info GrB_Matrix_kronecker_Semiring(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum,
                                        const GrB_Semiring op, const GrB_Matrix A, const GrB_Matrix B,
                                        const GrB_Descriptor desc);
+/* sort (reference core/ss/matrix.py:3991-4055, core/ss/vector.py:1562): every row of A (every
+ * column under GrB_DESC_T0) ordered by value.  C(i, r) is the value of rank r in row i and
+ * P(i, r) the column it came from, each row moved to columns 0 .. len(i)-1; under T0 C(r, j) and
+ * P(r, j) are the rank-r value and row index of column j.  C and P have A's shape in both orders.
+ * op is GrB_LT_<T> (ascending) or GrB_GT_<T> (descending) and compares the values cast to T;
+ * equal values (+0.0 and -0.0 are equal) keep ascending original index.  Where NaNs land is not
+ * specified.  No mask, no accumulator: C and P are replaced.  C takes the values cast to its
+ * type, P is GrB_INT64 or GrB_UINT64; either may be NULL (not computed), not both.  C or P may
+ * be A; C == P is GrB_NOT_IMPLEMENTED, as is any other BOOL-valued operator.  The vector form:
+ * w(k) is the rank-k value of u and p(k) its original index, k < nvals(u). */
+GrB_Info GxB_Matrix_sort(GrB_Matrix C, GrB_Matrix P, GrB_BinaryOp op, const GrB_Matrix A, const GrB_Descriptor desc);
+GrB_Info GxB_Vector_sort(GrB_Vector w, GrB_Vector p, GrB_BinaryOp op, const GrB_Vector u, const GrB_Descriptor desc);
 
 /* ---------------------------------------------------------------- the hot path */
 /* C<Mask> = C accum (A' (+).(x) B')      replaces SuiteSparse GrB_mxm */
@@ -511,7 +523,11 @@ GrB_Info GxB_MatrixMarket_read_coo(const char *path, GrB_Index *nrows, GrB_Index
                                    int *type_code, GrB_Index **I, GrB_Index **J, void **X);
 GrB_Info GxB_MatrixMarket_free(void *p);
 /* Backend selection knobs for benchmarking ablations: 0 = automatic ("kron_method": 1 = one
- * thread per output row in GrB_kronecker).  get_int also reads
+ * thread per output row in GrB_kronecker; "sort_method": 1 = every row of two or more entries
+ * through the segmented radix sort in GxB_Matrix_sort; "sort_wave_max" / "sort_block_max":
+ * the longest row of the sub-wave and of the workgroup class, which can only be lowered and
+ * read back as their defaults while unset).  get_int also reads "stat_sort_rows_wave" /
+ * "stat_sort_rows_block" / "stat_sort_rows_long" (rows each class took in the last sort),
  * the read-only counters "stat_bfs_spec_adopted" / "stat_bfs_spec_rollbacks" (BFS level
  * speculation) and "stat_nvals_copy" (vector counts read by a device copy
  * instead of the producing kernel's host mailbox). */
