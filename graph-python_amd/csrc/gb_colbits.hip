@@ -620,13 +620,6 @@ __global__ void k_cw_fill_iso(uint8_t *v, int64_t count, const uint8_t *one, int
         cb_copy(v + e * vsize, one, vsize);
 }
 
-unsigned cb_grid(int64_t items, unsigned cap) {
-    int64_t g = (items + CB_BLOCK - 1) / CB_BLOCK;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
-}
-
 unsigned long long *grid_state(int which) {
     unsigned long long *st = gb_device_state();
     return which == 0 ? st : st + GB_GRID2_OFFSET;
@@ -652,9 +645,9 @@ void to_cw(GB_Obj *A, const int64_t *srp, int64_t nsrp, const void *hint_key) {
         cwv = gb_malloc((size_t)vs * (size_t)k * (size_t)(n > 0 ? n : 1));
     }
     if (nv > 0) {
-        hipLaunchKernelGGL(k_csr_to_cw, dim3(cb_grid(nv, 2048)), dim3(CB_BLOCK), 0, gb_stream(), k, nv, A->rowptr,
-                           A->colidx, (const uint8_t *)A->vals, vs, cw, cw + n, iso ? nullptr : (uint8_t *)cwv, srp, nsrp,
-                           stat, grid_state(0));
+        hipLaunchKernelGGL(k_csr_to_cw, dim3(gb_grid(nv, CB_BLOCK, 2048)), dim3(CB_BLOCK), 0, gb_stream(), k, nv,
+                           A->rowptr, A->colidx, (const uint8_t *)A->vals, vs, cw, cw + n,
+                           iso ? nullptr : (uint8_t *)cwv, srp, nsrp, stat, grid_state(0));
         GB_LAUNCH_CHECK();
     }
     gb_drop_transpose(A);
@@ -682,8 +675,8 @@ void cw_expand(GB_Obj *A) {
     const int64_t count = A->nrows * A->ncols;
     uint8_t *v = (uint8_t *)gb_malloc((size_t)vs * (size_t)(count > 0 ? count : 1));
     if (count > 0) {
-        hipLaunchKernelGGL(k_cw_fill_iso, dim3(cb_grid(count, 4096)), dim3(CB_BLOCK), 0, gb_stream(), v, count,
-                           (const uint8_t *)A->cw_vals, vs);
+        hipLaunchKernelGGL(k_cw_fill_iso, dim3(gb_grid(count, CB_BLOCK, 4096)), dim3(CB_BLOCK), 0, gb_stream(), v,
+                           count, (const uint8_t *)A->cw_vals, vs);
         GB_LAUNCH_CHECK();
     }
     gb_free(A->cw_vals);
@@ -730,11 +723,11 @@ void gb_cw_materialize(GB_Obj *A) {
         d.x[l] = ls[l].x;
     }
     if (full && A->type->size == 4 && A->nrows % 4 == 0 && gb_knob("colbits_apply") != 2)
-        hipLaunchKernelGGL(k_cw_apply_layers_w4, dim3(cb_grid(A->ncols, 8192)), dim3(CB_BLOCK), 0, gb_stream(),
-                           A->ncols, (int)A->nrows, (int)ls.size(), d, (uint32_t *)A->cw_vals);
+        hipLaunchKernelGGL(k_cw_apply_layers_w4, dim3(gb_grid(A->ncols, CB_BLOCK, 8192)), dim3(CB_BLOCK), 0,
+                           gb_stream(), A->ncols, (int)A->nrows, (int)ls.size(), d, (uint32_t *)A->cw_vals);
     else
-        hipLaunchKernelGGL(k_cw_apply_layers, dim3(cb_grid(A->ncols, 2048)), dim3(CB_BLOCK), 0, gb_stream(), A->ncols,
-                           (int)A->nrows, (int)ls.size(), d, (uint8_t *)A->cw_vals, (int)A->type->size, full);
+        hipLaunchKernelGGL(k_cw_apply_layers, dim3(gb_grid(A->ncols, CB_BLOCK, 2048)), dim3(CB_BLOCK), 0, gb_stream(),
+                           A->ncols, (int)A->nrows, (int)ls.size(), d, (uint8_t *)A->cw_vals, (int)A->type->size, full);
     GB_LAUNCH_CHECK();
     for (auto &l : ls) gb_free(l.bits);
 }
@@ -773,11 +766,11 @@ void gb_cw_to_csr(GB_Obj *A) {
         int64_t *cptr = s.get<int64_t>(n + 1);
         int32_t *ridx = s.get<int32_t>(nv);
         uint8_t *tv = iso ? nullptr : s.get<uint8_t>((size_t)nv * vs);
-        hipLaunchKernelGGL(k_cw_pop, dim3(cb_grid(n, 4096)), dim3(CB_BLOCK), 0, gb_stream(), A->cw, n, pop);
+        hipLaunchKernelGGL(k_cw_pop, dim3(gb_grid(n, CB_BLOCK, 4096)), dim3(CB_BLOCK), 0, gb_stream(), A->cw, n, pop);
         GB_LAUNCH_CHECK();
         gb_exclusive_scan_i64(pop, cptr, n);
-        hipLaunchKernelGGL(k_cw_fill, dim3(cb_grid(n, 4096)), dim3(CB_BLOCK), 0, gb_stream(), A->cw, n, k, cptr, ridx,
-                           (const uint8_t *)A->cw_vals, tv, vs);
+        hipLaunchKernelGGL(k_cw_fill, dim3(gb_grid(n, CB_BLOCK, 4096)), dim3(CB_BLOCK), 0, gb_stream(), A->cw, n, k,
+                           cptr, ridx, (const uint8_t *)A->cw_vals, tv, vs);
         GB_LAUNCH_CHECK();
         // (n x k) CSR of A^T -> CSR of A
         gb_transpose_csr(n, k, nv, cptr, ridx, iso ? A->cw_vals : (const void *)tv, vs, iso, &rp, &ci, &vv);
@@ -841,8 +834,8 @@ bool gb_colbits_mxm(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_Semiring sr, G
     if (!A->cw) to_cw(A, sv.rowptr, inner, sv.rowptr);
     if (M && !M->cw) to_cw(M, nullptr, 0, nullptr);
     if (!A->hint_valid || A->hint_key != (const void *)sv.rowptr) {
-        hipLaunchKernelGGL(k_cw_hint, dim3(cb_grid(inner, 1024)), dim3(CB_BLOCK), 0, gb_stream(), A->cw, inner,
-                           sv.rowptr, A->cw_stat, grid_state(0));
+        hipLaunchKernelGGL(k_cw_hint, dim3(gb_grid(inner, CB_BLOCK, 1024)), dim3(CB_BLOCK), 0, gb_stream(), A->cw,
+                           inner, sv.rowptr, A->cw_stat, grid_state(0));
         GB_LAUNCH_CHECK();
         A->hint_valid = true;
         A->hint_key = sv.rowptr;
@@ -902,8 +895,8 @@ bool gb_colbits_mxm(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_Semiring sr, G
         gb_view_hot(pv, B, d.tran1 ? 0 : 1);
         if (pv.hcolidx) {
             Fhot = gb_malloc_n<uint64_t>(pv.nhot);
-            hipLaunchKernelGGL(k_cw_hot_gather, dim3(cb_grid(pv.nhot, 1024)), dim3(CB_BLOCK), 0, gb_stream(), a,
-                               pv.hcols, pv.nhot, Fhot);
+            hipLaunchKernelGGL(k_cw_hot_gather, dim3(gb_grid(pv.nhot, CB_BLOCK, 1024)), dim3(CB_BLOCK), 0, gb_stream(),
+                               a, pv.hcols, pv.nhot, Fhot);
             GB_LAUNCH_CHECK();
             a.pci = pv.hcolidx;
             a.Fhot = Fhot;
@@ -911,7 +904,7 @@ bool gb_colbits_mxm(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_Semiring sr, G
     }
     // enough waves to cover the output in a few chunks each; every block joins the grid sums
     const int64_t gcap = gb_knob("colbits_grid");
-    hipLaunchKernelGGL(k_cw_step, dim3(cb_grid((bc > inner ? bc : inner), gcap > 0 ? (unsigned)gcap : 2048)),
+    hipLaunchKernelGGL(k_cw_step, dim3(gb_grid((bc > inner ? bc : inner), CB_BLOCK, gcap > 0 ? (unsigned)gcap : 2048)),
                        dim3(CB_BLOCK), 0, gb_stream(), a);
     GB_LAUNCH_CHECK();
     gb_free(Fhot);  // stream-ordered
@@ -967,8 +960,8 @@ bool gb_colbits_assign_scalar(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, const vo
         // a value mask with per-entry values: read them, stamp eagerly
         gb_cw_materialize(M);
         gb_cw_materialize(C);
-        hipLaunchKernelGGL(k_cw_assign, dim3(cb_grid(n, 2048)), dim3(CB_BLOCK), 0, gb_stream(), n, (int)k, M->cw,
-                           nullptr, M->type->code, (const uint8_t *)M->cw_vals, (int)M->type->size, C->cw,
+        hipLaunchKernelGGL(k_cw_assign, dim3(gb_grid(n, CB_BLOCK, 2048)), dim3(CB_BLOCK), 0, gb_stream(), n, (int)k,
+                           M->cw, nullptr, M->type->code, (const uint8_t *)M->cw_vals, (int)M->type->size, C->cw,
                            (uint8_t *)C->cw_vals, xv, vs, C->cw_stat, grid_state(0));
         GB_LAUNCH_CHECK();
     } else {
@@ -984,8 +977,8 @@ bool gb_colbits_assign_scalar(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, const vo
         }
         const bool base_empty = nl == 0 && C->nvals_valid && C->nvals == 0;
         uint64_t *L = gb_malloc_n<uint64_t>(n > 0 ? n : 1);
-        hipLaunchKernelGGL(k_cw_assign_layer, dim3(cb_grid(n, 2048)), dim3(CB_BLOCK), 0, gb_stream(), n, M->cw, m_iso,
-                           M->type->code, C->cw, L, C->cw_stat, grid_state(0));
+        hipLaunchKernelGGL(k_cw_assign_layer, dim3(gb_grid(n, CB_BLOCK, 2048)), dim3(CB_BLOCK), 0, gb_stream(), n,
+                           M->cw, m_iso, M->type->code, C->cw, L, C->cw_stat, grid_state(0));
         GB_LAUNCH_CHECK();
         {
             std::lock_guard<std::mutex> lk(g_layers_mu);
@@ -1036,8 +1029,8 @@ GrB_Info GxB_Matrix_colwords_touch(GrB_Matrix A) {
         if (!o->pub) o->pub = gb_host_slot_alloc();
         const uint64_t seq = gb_next_pub_seq(o->pub);
         const int64_t n = o->ncols;
-        hipLaunchKernelGGL(k_cw_recount, dim3(cb_grid(n, 2048)), dim3(CB_BLOCK), 0, gb_stream(), o->cw, n, o->cw + n,
-                           o->cw_stat, grid_state(0), gb_host_slot_device(o->pub), (long long)seq);
+        hipLaunchKernelGGL(k_cw_recount, dim3(gb_grid(n, CB_BLOCK, 2048)), dim3(CB_BLOCK), 0, gb_stream(), o->cw, n,
+                           o->cw + n, o->cw_stat, grid_state(0), gb_host_slot_device(o->pub), (long long)seq);
         GB_LAUNCH_CHECK();
         o->nvals_valid = false;
         o->hint_valid = false;

@@ -557,6 +557,70 @@ GB_DEV T gb_shfl_down(T v, int delta, int width) {
 
 GB_DEV bool gb_bit(const uint64_t *bits, int64_t i) { return (bits[i >> 6] >> (i & 63)) & 1ULL; }
 
+// ------------------------------------------------------------------ loops and searches
+// Shared by every operation file (the host-side counterparts are in gb_dispatch.cuh):
+// the grid-stride loop, the searches over a CSR's row pointers and column indices, and a
+// wave's way from a chunk of entries to their rows.
+#define GB_GRID_LOOP(i, n) \
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
+
+// the unsigned word of VS bytes: values that are moved, never computed on (VS = 0, "nothing
+// to move", names a byte that is never touched)
+template <int VS>
+using gb_word_t = std::conditional_t<
+    VS == 8, uint64_t, std::conditional_t<VS == 4, uint32_t, std::conditional_t<VS == 2, uint16_t, uint8_t>>>;
+
+// first index in [lo, hi] whose rowptr exceeds p (rowptr[hi] > p is known): entry p is in
+// the row before it, the last r with rowptr[r] <= p -- which skips runs of empty rows
+GB_DEV int64_t gb_upper_bound(const int64_t *__restrict__ rowptr, int64_t lo, int64_t hi, int64_t p) {
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (rowptr[mid] > p) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+// first position in [lo, hi) of the sorted columns ci that holds j or more (hi: none does)
+template <class J>
+GB_DEV int64_t gb_lower_bound(const int32_t *__restrict__ ci, int64_t lo, int64_t hi, J j) {
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (ci[mid] < j) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// first idx >= start whose rowptr exceeds p, found by the whole wave (start <= the answer, and
+// rowptr[nrows] > p, are known): lane l looks at rowptr[start + l] (returned in *mine when
+// asked for, INT64_MAX past the end), a ballot finds the answer among those 64; further away
+// (a long run of empty rows), a binary search
+GB_DEV int64_t gb_wave_upper(const int64_t *__restrict__ rowptr, int64_t start, int64_t nrows, int64_t p, int lane,
+                             int64_t *mine = nullptr) {
+    const int64_t idx = start + lane;
+    const int64_t v = idx <= nrows ? rowptr[idx] : INT64_MAX;
+    if (mine) *mine = v;
+    const unsigned long long b = __ballot(v > p);
+    if (b) return start + (__ffsll(b) - 1);
+    return gb_upper_bound(rowptr, start + 64, nrows, p);
+}
+
+// A chunk of WPI * 64 entries whose row boundaries sit one per lane, as offsets into the chunk,
+// in rel of lanes first .. first + nb - 1: below[u] = the number of those boundaries at or
+// below the lane's u-th position u * 64 + lane (its row, counted from the chunk's first),
+// with one readlane per boundary.  nb <= 0 counts nothing.
+template <int WPI>
+GB_DEV void gb_count_bounds(int rel, int first, int nb, int lane, int (&below)[WPI]) {
+#pragma unroll
+    for (int u = 0; u < WPI; u++) below[u] = 0;
+    for (int t = first; t < first + nb; t++) {
+        const int r = __builtin_amdgcn_readlane(rel, t);
+#pragma unroll
+        for (int u = 0; u < WPI; u++) below[u] += r <= u * 64 + lane;
+    }
+}
+
 // (bool) of one value of runtime type `code` (mask semantics: -0.0 is false, NaN true)
 GB_DEV bool gb_dyn_nonzero(const void *p, int code) {
     switch (code) {

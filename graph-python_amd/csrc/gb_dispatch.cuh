@@ -1,6 +1,8 @@
 // gb_dispatch.cuh -- map a (semiring, input type, output type) triple to a
 // kernel instantiation: compile-time semirings for the configured hot paths,
-// the runtime-op semiring for every other builtin.
+// the runtime-op semiring for every other builtin.  Also the host-side dispatch every
+// operation file shares: by type code (gb_with_type), by value size (gb_with_size), by an
+// operator's (input, output) types (gb_dispatch_xz), and the host scalar cast.
 #pragma once
 #include "gb_device.cuh"
 #include "gb_internal.h"
@@ -34,6 +36,39 @@ static void gb_cast_scalar(void *out, int ct, const void *x, int xcode) {
             memcpy(out, &dv, sizeof(D));
         });
     });
+}
+
+// f(the unsigned word of `bytes` bytes), for kernels that move values without computing on them.
+// A size that is none of 1, 2, 4, 8 moves 8-byte words, or throws when the caller is strict.
+template <class F>
+static void gb_with_size(size_t bytes, F &&f, bool strict = false) {
+    switch (bytes) {
+    case 1: f(uint8_t()); break;
+    case 2: f(uint16_t()); break;
+    case 4: f(uint32_t()); break;
+    default:
+        GB_REQUIRE(bytes == 8 || !strict, GrB_NOT_IMPLEMENTED, "value size");
+        f(uint64_t());
+        break;
+    }
+}
+
+// f(X{}, Z{}) for a binary operator's input and output types: Z = X, or a comparison's BOOL
+template <class F>
+static void gb_dispatch_xz(int xcode, int zcode, F &&f) {
+    if (xcode == zcode) {
+        gb_with_type(xcode, [&](auto x) {
+            using X = decltype(x);
+            f(X{}, X{});
+        });
+    } else if (zcode == GBAMD_T_BOOL) {
+        gb_with_type(xcode, [&](auto x) {
+            using X = decltype(x);
+            f(X{}, bool{});
+        });
+    } else {
+        gb_throw(GrB_NOT_IMPLEMENTED, "operator type combination not supported");
+    }
 }
 
 struct gb_sr_info {

@@ -45,12 +45,7 @@ constexpr int DT_OVH_MIN = 64;    // the least per-entry cost (knob dot_ovh): si
 constexpr int DT_WIN = 32768;     // task window: <= DT_WIN / ovh entries start in one
 constexpr int DT_MAXE = DT_WIN / DT_OVH_MIN;
 
-static inline unsigned dt_grid(int64_t n, int per_block = DT_BLOCK, int64_t cap = 1 << 16) {
-    int64_t g = (n + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
-}
+constexpr int64_t DT_GRID_CAP = 1 << 16;  // blocks, unless the launch names its own cap
 
 // one phase's view: groups (rows of the mask for R, its columns for C), the
 // longer lists X (indexed by group) and the shorter lists Y (indexed by the
@@ -1192,7 +1187,7 @@ int64_t gb_dot_two_sided(const gb_csr_view &A, const gb_csr_view &BT, gb_mmask &
                                 BT.iso};
             const dt_vals<X> xv = SWAP ? vb : va, yv = SWAP ? va : vb;
             if (!SWAP && SRT::reads_values && (va.nk || vb.nk)) gb_stat_add("dot_narrow_calls", 1);
-            const unsigned gw = dt_grid(sd.ng * 64, DT_BLOCK, 1 << 15);
+            const unsigned gw = gb_grid(sd.ng * 64, DT_BLOCK, 1 << 15);
             // 1: one entry at a time (the round-5 loop, A/B)
             const int sseq = gb_knob("dot_small_seq") == 1 ? 1 : 0;
             hipLaunchKernelGGL((k_dot_small<SRT, X, Z, SWAP, 1>), dim3(gw), dim3(DT_BLOCK), 0, gb_stream(), srf,
@@ -1218,8 +1213,8 @@ int64_t gb_dot_two_sided(const gb_csr_view &A, const gb_csr_view &BT, gb_mmask &
             if (hubc) {
                 int32_t *nch = hcs.get<int32_t>(sd.ng);
                 hcp = hcs.get<int64_t>(sd.ng + 1);
-                hipLaunchKernelGGL(k_dt_hub_count, dim3(dt_grid(sd.ng)), dim3(DT_BLOCK), 0, gb_stream(), sd, cap, nch,
-                                   amax);
+                hipLaunchKernelGGL(k_dt_hub_count, dim3(gb_grid(sd.ng, DT_BLOCK, DT_GRID_CAP)), dim3(DT_BLOCK), 0,
+                                   gb_stream(), sd, cap, nch, amax);
                 GB_LAUNCH_CHECK();
                 gb_exclusive_scan_i32(nch, 0, hcp, sd.ng);
                 nhch = gb_read_i64(hcp + sd.ng);
@@ -1240,15 +1235,15 @@ int64_t gb_dot_two_sided(const gb_csr_view &A, const gb_csr_view &BT, gb_mmask &
                     int32_t *key = ts.get<int32_t>(ne);
                     int64_t *idx = ts.get<int64_t>(ne);
                     const int64_t ytot = gb_read_i64(sd.yrp + (SWAP ? A.nrows : BT.nrows));
-                    hipLaunchKernelGGL(k_dt_ykey, dim3(dt_grid(ne)), dim3(DT_BLOCK), 0, gb_stream(), ne, (int)K, ytot,
-                                       eYS, key, idx);
+                    hipLaunchKernelGGL(k_dt_ykey, dim3(gb_grid(ne, DT_BLOCK, DT_GRID_CAP)), dim3(DT_BLOCK), 0,
+                                       gb_stream(), ne, (int)K, ytot, eYS, key, idx);
                     GB_LAUNCH_CHECK();
                     gb_sort_pairs_i32(key, idx, ne, bits);  // stable: G order inside a block
                     auto perm = [&](auto *arr) {
                         using T = std::remove_pointer_t<decltype(arr)>;
                         T *tmp = gb_malloc_n<T>(ne);
-                        hipLaunchKernelGGL(k_dt_gather<T>, dim3(dt_grid(ne)), dim3(DT_BLOCK), 0, gb_stream(), ne, idx,
-                                           (const T *)arr, tmp);
+                        hipLaunchKernelGGL(k_dt_gather<T>, dim3(gb_grid(ne, DT_BLOCK, DT_GRID_CAP)), dim3(DT_BLOCK), 0,
+                                           gb_stream(), ne, idx, (const T *)arr, tmp);
                         GB_LAUNCH_CHECK();
                         gb_copy_d2d(arr, tmp, ne * sizeof(T));
                         gb_free(tmp);
@@ -1263,18 +1258,18 @@ int64_t gb_dot_two_sided(const gb_csr_view &A, const gb_csr_view &BT, gb_mmask &
                 int64_t *cum = ts.get<int64_t>(ne + 1);
                 gb_exclusive_scan_i32(eB, (int)ovh, cum, ne);
                 uint8_t *tsf = ts.get<uint8_t>(ne);
-                hipLaunchKernelGGL(k_dt_task_flags, dim3(dt_grid(ne)), dim3(DT_BLOCK), 0, gb_stream(), ne, win, eG,
-                                   ePc, cum, tsf);
+                hipLaunchKernelGGL(k_dt_task_flags, dim3(gb_grid(ne, DT_BLOCK, DT_GRID_CAP)), dim3(DT_BLOCK), 0,
+                                   gb_stream(), ne, win, eG, ePc, cum, tsf);
                 int64_t *tpos = ts.get<int64_t>(ne + 1);
                 gb_exclusive_scan_u8(tsf, tpos, ne);
                 const int64_t nt = gb_read_i64(tpos + ne);
                 int64_t *tstart = ts.get<int64_t>(nt + 1);
-                hipLaunchKernelGGL(k_dt_task_fill, dim3(dt_grid(ne)), dim3(DT_BLOCK), 0, gb_stream(), ne, tsf, tpos,
-                                   tstart);
+                hipLaunchKernelGGL(k_dt_task_fill, dim3(gb_grid(ne, DT_BLOCK, DT_GRID_CAP)), dim3(DT_BLOCK), 0,
+                                   gb_stream(), ne, tsf, tpos, tstart);
                 GB_LAUNCH_CHECK();
                 dt_task *tdesc = ts.get<dt_task>(nt);
-                hipLaunchKernelGGL(k_dt_task_desc, dim3(dt_grid(nt)), dim3(DT_BLOCK), 0, gb_stream(), nt, tstart, eG,
-                                   ePc, sd.xrp, cap, tdesc);
+                hipLaunchKernelGGL(k_dt_task_desc, dim3(gb_grid(nt, DT_BLOCK, DT_GRID_CAP)), dim3(DT_BLOCK), 0,
+                                   gb_stream(), nt, tstart, eG, ePc, sd.xrp, cap, tdesc);
                 GB_LAUNCH_CHECK();
                 // persistent workgroups (two per CU) taking chunks of consecutive tasks
                 const unsigned gt = (unsigned)std::min<int64_t>(nt, 1024);
@@ -1326,8 +1321,8 @@ int64_t gb_dot_two_sided(const gb_csr_view &A, const gb_csr_view &BT, gb_mmask &
             if (pmin <= 0) pmin = 131072;
             if (gb_knob("dot_dbg") & 16) fprintf(stderr, "dot phase %d: %lld huge entries\n", (int)SWAP, (long long)nh);
             if (nh < pmin) {
-                hipLaunchKernelGGL(k_dt_huge_to_csr, dim3(dt_grid(nm)), dim3(DT_BLOCK), 0, gb_stream(), nm, hg, sd.perm,
-                                   hflag);
+                hipLaunchKernelGGL(k_dt_huge_to_csr, dim3(gb_grid(nm, DT_BLOCK, DT_GRID_CAP)), dim3(DT_BLOCK), 0,
+                                   gb_stream(), nm, hg, sd.perm, hflag);
                 GB_LAUNCH_CHECK();
                 return;
             }
@@ -1347,15 +1342,15 @@ int64_t gb_dot_two_sided(const gb_csr_view &A, const gb_csr_view &BT, gb_mmask &
             Z ident = Z();
             if (!(std::is_same<SRT, gb_sr_any_pair<Z>>::value || info.mon == GBAMD_MON_ANY))
                 ident = gb_monoid_identity<Z>(info.mon);
-            hipLaunchKernelGGL((k_dt_ident<Z>), dim3(dt_grid(nh)), dim3(DT_BLOCK), 0, gb_stream(), nh, hQ, (Z *)tval,
-                               ident);
+            hipLaunchKernelGGL((k_dt_ident<Z>), dim3(gb_grid(nh, DT_BLOCK, DT_GRID_CAP)), dim3(DT_BLOCK), 0,
+                               gb_stream(), nh, hQ, (Z *)tval, ident);
             GB_LAUNCH_CHECK();
             const int64_t amx = gb_read_i64((const int64_t *)amax);
             const int64_t np = (amx + cap - 1) / cap;
             if (np > 65535) {  // the piece index travels as 16 bits (ePc): such lists (> 2^29 keys)
                                // go to the per-entry kernel
-                hipLaunchKernelGGL(k_dt_huge_to_csr, dim3(dt_grid(nm)), dim3(DT_BLOCK), 0, gb_stream(), nm, hg,
-                                   sd.perm, hflag);
+                hipLaunchKernelGGL(k_dt_huge_to_csr, dim3(gb_grid(nm, DT_BLOCK, DT_GRID_CAP)), dim3(DT_BLOCK), 0,
+                                   gb_stream(), nm, hg, sd.perm, hflag);
                 GB_LAUNCH_CHECK();
                 return;
             }
@@ -1365,8 +1360,8 @@ int64_t gb_dot_two_sided(const gb_csr_view &A, const gb_csr_view &BT, gb_mmask &
             int64_t *P = hs.get<int64_t>(nh + 1);
             {
                 int64_t *npc = hs.get<int64_t>(nh);
-                hipLaunchKernelGGL(k_dt_piece_count, dim3(dt_grid(nh)), dim3(DT_BLOCK), 0, gb_stream(), sd, nh, cap,
-                                   hG, npc);
+                hipLaunchKernelGGL(k_dt_piece_count, dim3(gb_grid(nh, DT_BLOCK, DT_GRID_CAP)), dim3(DT_BLOCK), 0,
+                                   gb_stream(), sd, nh, cap, hG, npc);
                 GB_LAUNCH_CHECK();
                 gb_exclusive_scan_i64(npc, P, nh);
             }
@@ -1375,8 +1370,8 @@ int64_t gb_dot_two_sided(const gb_csr_view &A, const gb_csr_view &BT, gb_mmask &
             int64_t *ppos = hs.get<int64_t>(npairs + 1);
             int64_t *pys = hs.get<int64_t>(npairs);
             int32_t *pb = hs.get<int32_t>(npairs);
-            hipLaunchKernelGGL(k_dt_piece_flags, dim3(dt_grid(nh)), dim3(DT_BLOCK), 0, gb_stream(), sd, nh, cap, hG,
-                               hYS, hB, P, pos, pc, pys, pb);
+            hipLaunchKernelGGL(k_dt_piece_flags, dim3(gb_grid(nh, DT_BLOCK, DT_GRID_CAP)), dim3(DT_BLOCK), 0,
+                               gb_stream(), sd, nh, cap, hG, hYS, hB, P, pos, pc, pys, pb);
             GB_LAUNCH_CHECK();
             gb_exclusive_scan_i32(pc, 0, ppos, npairs);
             const int64_t npe = gb_read_i64(ppos + npairs);
@@ -1389,8 +1384,9 @@ int64_t gb_dot_two_sided(const gb_csr_view &A, const gb_csr_view &BT, gb_mmask &
             int32_t *eB = ps.get<int32_t>(npe);
             int64_t *eQ = ps.get<int64_t>(npe);
             uint16_t *ePc = ps.get<uint16_t>(npe);
-            hipLaunchKernelGGL(k_dt_piece_compact, dim3(dt_grid(nh)), dim3(DT_BLOCK), 0, gb_stream(), sd, nh, cap, hG,
-                               hO, hQ, P, pos, pc, ppos, pys, pb, eG, eYS, eO, eB, eQ, ePc);
+            hipLaunchKernelGGL(k_dt_piece_compact, dim3(gb_grid(nh, DT_BLOCK, DT_GRID_CAP)), dim3(DT_BLOCK), 0,
+                               gb_stream(), sd, nh, cap, hG, hO, hQ, P, pos, pc, ppos, pys, pb, eG, eYS, eO, eB, eQ,
+                               ePc);
             GB_LAUNCH_CHECK();
             run_tasks(npe, eG, eYS, eO, eB, eQ, ePc);
         };
@@ -1404,7 +1400,8 @@ int64_t gb_dot_two_sided(const gb_csr_view &A, const gb_csr_view &BT, gb_mmask &
     gb_stat_add("dot_huge_entries", nh);
     if (nh) {
         int64_t *hq = gb_malloc_n<int64_t>(nh);
-        hipLaunchKernelGGL(k_dt_positions, dim3(dt_grid(nm)), dim3(DT_BLOCK), 0, gb_stream(), nm, hflag, pos, hq);
+        hipLaunchKernelGGL(k_dt_positions, dim3(gb_grid(nm, DT_BLOCK, DT_GRID_CAP)), dim3(DT_BLOCK), 0, gb_stream(), nm,
+                           hflag, pos, hq);
         GB_LAUNCH_CHECK();
         *huge = hq;
     }

@@ -57,20 +57,15 @@ void gb_expand_indices(gb_index_list &L, const GrB_Index *I, GrB_Index ni, int64
 }
 
 // ------------------------------------------------------------------ kernels
-static inline unsigned ext_grid(int64_t items, int64_t per_block, unsigned cap = 65535) {
-    int64_t g = (items + per_block - 1) / per_block;
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(g, cap));
-}
-
 // jcnt[c] = number of positions p with J[p] == c
 __global__ void k_ext_jcount(int64_t nj, const int64_t *__restrict__ J, int32_t *__restrict__ jcnt) {
-    for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < nj; p += (int64_t)gridDim.x * blockDim.x)
+    GB_GRID_LOOP(p, nj)
         atomicAdd(&jcnt[J[p]], 1);
 }
 // jpos[jptr[c] ...] = the positions p with J[p] == c (any order: the output sort fixes it)
 __global__ void k_ext_jfill(int64_t nj, const int64_t *__restrict__ J, int64_t *__restrict__ cursor,
                             int32_t *__restrict__ jpos) {
-    for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < nj; p += (int64_t)gridDim.x * blockDim.x)
+    GB_GRID_LOOP(p, nj)
         jpos[atomicAdd((unsigned long long *)&cursor[J[p]], 1ULL)] = (int32_t)p;
 }
 
@@ -128,7 +123,7 @@ __global__ __launch_bounds__(EXT_BLOCK) void k_ext_rows(int64_t ni, const int64_
 template <class V>
 __global__ void k_ext_finish(int64_t nz, const uint64_t *__restrict__ key, const int64_t *__restrict__ src,
                              const V *__restrict__ vin, int32_t *__restrict__ colidx, V *__restrict__ vout) {
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nz; t += (int64_t)gridDim.x * blockDim.x) {
+    GB_GRID_LOOP(t, nz) {
         colidx[t] = (int32_t)(key[t] & 0xffffffffULL);
         if (vout) vout[t] = vin[src[t]];
     }
@@ -165,28 +160,12 @@ __global__ __launch_bounds__(EXT_BLOCK) void k_ext_col(int64_t nk, const int64_t
         bool hit = false;
         if (k < nk) {
             const int64_t c = I ? I[k] : k;
-            int64_t lo = e0, hi = e1;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (ci[mid] < c) lo = mid + 1;
-                else hi = mid;
-            }
+            const int64_t lo = gb_lower_bound(ci, e0, e1, c);
             hit = lo < e1 && ci[lo] == c;
             if (hit && wvals) wvals[k] = vin[lo];
         }
         const uint64_t word = __ballot(hit);
         if (lane == 0) wbits[k >> 6] = word;
-    }
-}
-
-template <class F>
-static void with_size(size_t ts, F &&f) {
-    switch (ts) {
-    case 1: f(uint8_t()); break;
-    case 2: f(uint16_t()); break;
-    case 4: f(uint32_t()); break;
-    case 8: f(uint64_t()); break;
-    default: gb_throw(GrB_NOT_IMPLEMENTED, "value size");
     }
 }
 
@@ -215,19 +194,19 @@ static void extract_csr(gb_mat_result &T, const gb_csr_view &v, const gb_index_l
     if (!LJ.all) {
         int32_t *jcnt = s.get<int32_t>(v.ncols);
         gb_memset(jcnt, 0, v.ncols * sizeof(int32_t));
-        if (nj) hipLaunchKernelGGL(k_ext_jcount, dim3(ext_grid(nj, EXT_BLOCK, 4096)), dim3(EXT_BLOCK), 0, gb_stream(),
+        if (nj) hipLaunchKernelGGL(k_ext_jcount, dim3(gb_grid(nj, EXT_BLOCK, 4096)), dim3(EXT_BLOCK), 0, gb_stream(),
                                    nj, dJ, jcnt);
         int64_t *jp = s.get<int64_t>(v.ncols + 1);
         gb_exclusive_scan_i32(jcnt, 0, jp, v.ncols);
         int64_t *cursor = s.get<int64_t>(v.ncols + 1);
         gb_copy_d2d(cursor, jp, (v.ncols + 1) * sizeof(int64_t));
         jpos = s.get<int32_t>(nj);
-        if (nj) hipLaunchKernelGGL(k_ext_jfill, dim3(ext_grid(nj, EXT_BLOCK, 4096)), dim3(EXT_BLOCK), 0, gb_stream(),
+        if (nj) hipLaunchKernelGGL(k_ext_jfill, dim3(gb_grid(nj, EXT_BLOCK, 4096)), dim3(EXT_BLOCK), 0, gb_stream(),
                                    nj, dJ, cursor, jpos);
         jptr = jp;
     }
     int64_t *cnt = s.get<int64_t>(ni + 1);
-    const unsigned grid = ext_grid(ni, EXT_BLOCK / 64, 16384);
+    const unsigned grid = gb_grid(ni, EXT_BLOCK / 64, 16384);
     if (ni) {
         if (LJ.all)
             hipLaunchKernelGGL((k_ext_rows<true, false>), dim3(grid), dim3(EXT_BLOCK), 0, gb_stream(), ni, dI,
@@ -258,24 +237,13 @@ static void extract_csr(gb_mat_result &T, const gb_csr_view &v, const gb_index_l
             while (bits < 64 && (1LL << (bits - 32)) < ni) bits++;
             gb_sort_pairs_u64(key, src, nz, bits);
         }
-        with_size(ts, [&](auto z) {
+        gb_with_size(ts, [&](auto z) {
             using V = decltype(z);
-            hipLaunchKernelGGL((k_ext_finish<V>), dim3(ext_grid(nz, EXT_BLOCK, 16384)), dim3(EXT_BLOCK), 0,
+            hipLaunchKernelGGL((k_ext_finish<V>), dim3(gb_grid(nz, EXT_BLOCK, 16384)), dim3(EXT_BLOCK), 0,
                                gb_stream(), nz, key, src, (const V *)v.vals, T.colidx, v.iso ? nullptr : (V *)T.vals);
-        });
+        }, true);  // any other size: not implemented
         GB_LAUNCH_CHECK();
     }
-}
-
-static gb_vec_result empty_vec_result(int64_t n, int code, bool iso) {
-    gb_vec_result T;
-    T.n = n;
-    T.tcode = code;
-    T.iso = iso;
-    T.bits = gb_malloc_n<uint64_t>(gb_words(n) ? gb_words(n) : 1);
-    T.dense = gb_malloc((iso ? 1 : std::max<int64_t>(n, 1)) * gb_type_size(code));
-    T.d_nvals = gb_malloc_n<int64_t>(1);
-    return T;
 }
 
 extern "C" {
@@ -320,16 +288,16 @@ GrB_Info GrB_Col_extract(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp
         const int64_t *dI = upload_list(LI, s);
         int64_t e[2];
         gb_copy_d2h(e, v.rowptr + j, 2 * sizeof(int64_t));
-        gb_vec_result T = empty_vec_result(LI.n, v.tcode, v.iso);
+        gb_vec_result T = gb_new_vec_result(LI.n, v.tcode, v.iso);
         const size_t ts = gb_type_size(v.tcode);
         if (v.iso) gb_copy_d2d(T.dense, v.vals, ts);
         if (LI.n) {
-            with_size(ts, [&](auto z) {
+            gb_with_size(ts, [&](auto z) {
                 using V = decltype(z);
-                hipLaunchKernelGGL((k_ext_col<V>), dim3(ext_grid(LI.n, EXT_BLOCK, 16384)), dim3(EXT_BLOCK), 0,
+                hipLaunchKernelGGL((k_ext_col<V>), dim3(gb_grid(LI.n, EXT_BLOCK, 16384)), dim3(EXT_BLOCK), 0,
                                    gb_stream(), LI.n, dI, v.colidx, e[0], e[1], (const V *)v.vals, T.bits,
                                    v.iso ? nullptr : (V *)T.dense);
-            });
+            }, true);  // any other size: not implemented
             GB_LAUNCH_CHECK();
         }
         gb_bitmap_count(T.bits, LI.n, T.d_nvals);
@@ -358,16 +326,16 @@ GrB_Info GrB_Vector_extract(GrB_Vector w, const GrB_Vector mask, const GrB_Binar
             gb_copy_h2d(d, ident.data(), LI.n * sizeof(int64_t));
             dI = d;
         }
-        gb_vec_result T = empty_vec_result(LI.n, uv.tcode, uv.iso);
+        gb_vec_result T = gb_new_vec_result(LI.n, uv.tcode, uv.iso);
         const size_t ts = gb_type_size(uv.tcode);
         if (uv.iso) gb_copy_d2d(T.dense, uv.vals, ts);
         if (LI.n) {
-            with_size(ts, [&](auto z) {
+            gb_with_size(ts, [&](auto z) {
                 using V = decltype(z);
-                hipLaunchKernelGGL((k_ext_vec<V>), dim3(ext_grid(LI.n, EXT_BLOCK, 16384)), dim3(EXT_BLOCK), 0,
+                hipLaunchKernelGGL((k_ext_vec<V>), dim3(gb_grid(LI.n, EXT_BLOCK, 16384)), dim3(EXT_BLOCK), 0,
                                    gb_stream(), LI.n, dI, uv.bits, (const V *)uv.vals, T.bits,
                                    uv.iso ? nullptr : (V *)T.dense);
-            });
+            }, true);  // any other size: not implemented
             GB_LAUNCH_CHECK();
         }
         gb_bitmap_count(T.bits, LI.n, T.d_nvals);

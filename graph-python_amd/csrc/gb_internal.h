@@ -284,6 +284,12 @@ void gb_sync();
 int64_t gb_knob(const char *key);
 // persistent zeroed device words (layout: gb_state.h), allocated on first use
 unsigned long long *gb_device_state();
+// blocks of a launch: ceil(items / per_block) clamped to [1, cap].  A launch that counts waves
+// passes per_block = BLOCK / 64.  The caps differ per file and per kernel: they are tuned.
+inline unsigned gb_grid(int64_t items, int64_t per_block, int64_t cap) {
+    const int64_t g = (items + per_block - 1) / per_block;
+    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
+}
 
 // Host-visible mailboxes in pinned coherent memory: a kernel publishes a
 // device count with a sequence number (system-scope store); the host spins on
@@ -606,7 +612,41 @@ void gb_exclusive_scan_i32(const int32_t *in, int64_t add_each, int64_t *out, in
 void gb_sort_pairs_u64(uint64_t *keys, int64_t *vals, int64_t n, int end_bit);
 void gb_sort_pairs_i32(int32_t *keys, int64_t *vals, int64_t n, int end_bit);
 int64_t gb_read_i64(const int64_t *dptr);
+// out[e - pbase] = the row of entry e, for the entries of rows [r0, r1): a wave per row, in a
+// grid of at most grid_cap blocks (the callers' caps differ)
+void gb_rows_of(const int64_t *rowptr, int64_t r0, int64_t r1, int64_t pbase, int64_t *out, int64_t grid_cap);
 
 const char *gb_type_name(int code);
 size_t gb_type_size(int code);
 GrB_Type gb_type_of(int code);
+
+// ------------------------------------------------------------------ result skeletons
+// the buffers of a result of this shape: one value when iso, and no allocation of zero bytes
+inline gb_vec_result gb_new_vec_result(int64_t n, int tcode, bool iso) {
+    gb_vec_result T;
+    T.n = n;
+    T.tcode = tcode;
+    T.iso = iso;
+    T.bits = gb_malloc_n<uint64_t>(gb_words(n) ? gb_words(n) : 1);
+    T.dense = gb_malloc((iso || n < 1 ? 1 : n) * gb_type_size(tcode));
+    T.d_nvals = gb_malloc_n<int64_t>(1);
+    return T;
+}
+inline gb_mat_result gb_new_mat_result(int64_t nrows, int64_t ncols, int tcode, int64_t nvals, bool iso) {
+    gb_mat_result T;
+    T.nrows = nrows;
+    T.ncols = ncols;
+    T.tcode = tcode;
+    T.nvals = nvals;
+    T.iso = iso;
+    T.rowptr = gb_malloc_n<int64_t>(nrows + 1);
+    T.colidx = gb_malloc_n<int32_t>(nvals < 1 ? 1 : nvals);
+    T.vals = gb_malloc((iso || nvals < 1 ? 1 : nvals) * gb_type_size(tcode));
+    return T;
+}
+// the matrix result of this shape without entries (no call site builds an empty vector result)
+inline gb_mat_result gb_empty_mat_result(int64_t nrows, int64_t ncols, int tcode) {
+    gb_mat_result T = gb_new_mat_result(nrows, ncols, tcode, 0, false);
+    gb_memset(T.rowptr, 0, (nrows + 1) * sizeof(int64_t));
+    return T;
+}

@@ -11,9 +11,9 @@
 //                   of entries in one output row): a wave owns a contiguous run of chunks of
 //                   KRON_CHUNK output positions, lane l of step u fills position
 //                   p0 + 64 u + l, so stores are coalesced and columns ascend within a row
-//                   with no sort.  The rows of a chunk are found in rowptrT as k_select_mark
-//                   finds them (gb_select.hip): the wave bounds the chunk's first and last
-//                   row (skipping runs of empty rows), lane l then owns row rlo - 1 + l and
+//                   with no sort.  The rows of a chunk are found in rowptrT with the helpers
+//                   k_select_mark uses (gb_wave_upper, gb_count_bounds of gb_device.cuh): the
+//                   wave bounds the chunk's first and last row, lane l then owns row rlo - 1 + l and
 //                   does that row's divides once -- row -> (iA, iB), and the A entry / B
 //                   offset of the row's first position inside the chunk.  An entry at
 //                   distance d < KRON_CHUNK from there is A entry + (rb + d) / lenB, B entry
@@ -54,28 +54,6 @@ GB_DEV void kron_divmod(int64_t n, int64_t d, int64_t *q, int64_t *r) {
     }
 }
 
-// first index in [lo, hi] whose rowptr exceeds p (rowptr[hi] > p is known)
-GB_DEV int64_t kron_upper(const int64_t *__restrict__ rowptr, int64_t lo, int64_t hi, int64_t p) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (rowptr[mid] > p) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// first idx >= start whose rowptr exceeds p, found by the whole wave (start <= the answer, and
-// rowptr[nrows] > p, are known): lane l looks at rowptr[start + l], a ballot finds the answer
-// among those 64; further away (a long run of empty rows), a binary search
-GB_DEV int64_t kron_wave_upper(const int64_t *__restrict__ rowptr, int64_t start, int64_t nrows, int64_t p,
-                               int lane) {
-    const int64_t idx = start + lane;
-    const int64_t v = idx <= nrows ? rowptr[idx] : INT64_MAX;
-    const unsigned long long b = __ballot(v > p);
-    if (b) return start + (__ffsll(b) - 1);
-    return kron_upper(rowptr, start + 64, nrows, p);
-}
-
 // the entry-parallel kernel writes its output once, coalesced, and never reads it back: its
 // stores are nontemporal (NT); the per-row kernel's scattered stores stay plain
 template <bool NT, class T>
@@ -101,19 +79,6 @@ struct kron_compute {
 
 // VS: bytes per value, 0 = no values to write (iso result)
 template <int VS>
-struct kron_word;
-template <>
-struct kron_word<0> { using type = uint8_t; };
-template <>
-struct kron_word<1> { using type = uint8_t; };
-template <>
-struct kron_word<2> { using type = uint16_t; };
-template <>
-struct kron_word<4> { using type = uint32_t; };
-template <>
-struct kron_word<8> { using type = uint64_t; };
-
-template <int VS>
 struct kron_move {
     const void *src;  // the values of A' (FIRST) or of B' (SECOND, ANY), one per entry
     bool from_b;
@@ -121,7 +86,7 @@ struct kron_move {
     template <bool NT>
     GB_DEV void put(int64_t t, int64_t a, int64_t b) const {
         if (VS) {
-            using W = typename kron_word<VS>::type;
+            using W = gb_word_t<VS>;
             kron_store<NT, W>(&((W *)dst)[t], ((const W *)src)[from_b ? b : a]);
         }
     }
@@ -131,6 +96,7 @@ __global__ __launch_bounds__(KRON_BLOCK) void k_kron_rowptr(int64_t nrT, int64_t
                                                             const int64_t *__restrict__ rpA,
                                                             const int64_t *__restrict__ rpB,
                                                             int64_t *__restrict__ rpT) {
+    // (the block size as a constant, not GB_GRID_LOOP's blockDim.x: two scalar registers apart)
     for (int64_t R = blockIdx.x * (int64_t)KRON_BLOCK + threadIdx.x; R <= nrT; R += (int64_t)gridDim.x * KRON_BLOCK) {
         if (R == nrT) {
             rpT[R] = nvA * nvB;
@@ -168,8 +134,8 @@ __global__ __launch_bounds__(KRON_BLOCK) void k_kron_fill(int64_t nvT, int64_t n
         const int64_t p0 = g * KRON_CHUNK;
         const int64_t plast = min(p0 + KRON_CHUNK, nvT) - 1;
         // rows rlo - 1 .. rhi - 1 hold the chunk; rpT[rlo .. rhi) are the boundaries inside it
-        const int64_t rlo = next < 0 ? kron_upper(rpT, 1, nrT, p0) : kron_wave_upper(rpT, next, nrT, p0, lane);
-        const int64_t rhi = kron_wave_upper(rpT, rlo, nrT, plast, lane);
+        const int64_t rlo = next < 0 ? gb_upper_bound(rpT, 1, nrT, p0) : gb_wave_upper(rpT, next, nrT, p0, lane);
+        const int64_t rhi = gb_wave_upper(rpT, rlo, nrT, plast, lane);
         next = rhi;
         if (rhi - rlo < 64) {
             const int nb = (int)(rhi - rlo);
@@ -196,15 +162,9 @@ __global__ __launch_bounds__(KRON_BLOCK) void k_kron_fill(int64_t nvT, int64_t n
                 lb = (uint32_t)lenB;
                 rcp = __builtin_amdgcn_rcpf((float)lenB);
             }
-            // an entry's row slot: the number of boundaries at or below it
+            // an entry's row slot: the number of boundaries (lanes 1 .. nb) at or below it
             int slot[KRON_WPI];
-#pragma unroll
-            for (int u = 0; u < KRON_WPI; u++) slot[u] = 0;
-            for (int t = 1; t <= nb; t++) {
-                const int r = __builtin_amdgcn_readlane(rel, t);
-#pragma unroll
-                for (int u = 0; u < KRON_WPI; u++) slot[u] += r <= u * 64 + lane;
-            }
+            gb_count_bounds<KRON_WPI>(rel, 1, nb, lane, slot);
 #pragma unroll
             for (int u = 0; u < KRON_WPI; u++) {
                 const int o = u * 64 + lane;
@@ -237,7 +197,7 @@ __global__ __launch_bounds__(KRON_BLOCK) void k_kron_fill(int64_t nvT, int64_t n
             for (int u = 0; u < KRON_WPI; u++) {
                 const int64_t t = p0 + u * 64 + lane;
                 if (t >= nvT) continue;
-                const int64_t R = kron_upper(rpT, rlo, rhi, t) - 1;
+                const int64_t R = gb_upper_bound(rpT, rlo, rhi, t) - 1;
                 int64_t iA, iB, qa, r0;
                 kron_divmod(R, p, &iA, &iB);
                 const int64_t b0 = rpB[iB];
@@ -274,45 +234,12 @@ __global__ __launch_bounds__(KRON_BLOCK) void k_kron_rows(int64_t nrT, int64_t p
     }
 }
 
-unsigned kron_grid(int64_t nwaves_wanted) {
-    int64_t g = (nwaves_wanted + KRON_BLOCK / 64 - 1) / (KRON_BLOCK / 64);
-    int64_t cap = gb_knob("kron_grid");  // tests: few blocks, so that a wave runs through many chunks
-    if (cap <= 0 || cap > 8192) cap = 8192;
-    return (unsigned)std::min<int64_t>(std::max<int64_t>(g, 1), cap);
-}
-
-// the operator's (X, Z) pairs: Z = X, or a comparison's BOOL (as eWise, gb_ops.hip dispatch_xz)
-template <class F>
-void kron_dispatch_xz(int xcode, int zcode, F &&f) {
-    if (xcode == zcode) {
-        gb_with_type(xcode, [&](auto x) {
-            using X = decltype(x);
-            f(X{}, X{});
-        });
-    } else if (zcode == GBAMD_T_BOOL) {
-        gb_with_type(xcode, [&](auto x) {
-            using X = decltype(x);
-            f(X{}, bool{});
-        });
-    } else {
-        gb_throw(GrB_NOT_IMPLEMENTED, "operator type combination not supported");
-    }
-}
-
-void kron_check_binop(GrB_BinaryOp op, bool allow_null) {
-    if (!op) {
-        GB_REQUIRE(allow_null, GrB_NULL_POINTER, "operator is NULL");
-        return;
-    }
-    GB_REQUIRE(op->magic == GB_MAGIC, GrB_UNINITIALIZED_OBJECT, "invalid operator");
-}
-
 }  // namespace
 
 void gb_kronecker(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_BinaryOp op, GB_Obj *A, GB_Obj *B,
                   const gb_desc &d) {
-    kron_check_binop(op, false);
-    kron_check_binop(accum, true);
+    gb_check_binop(op, false);
+    gb_check_binop(accum, true);
     GB_REQUIRE(op->xtype != nullptr, GrB_NOT_IMPLEMENTED, "positional kronecker operator");
     const int xcode = op->xtype->code, zcode = op->ztype->code, opc = op->opcode;
     gb_csr_view av, bv;
@@ -332,29 +259,26 @@ void gb_kronecker(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_BinaryOp op, GB_
     const bool use_b = opc != GBAMD_OP_FIRST && opc != GBAMD_OP_PAIR;
     const bool t_iso = nvT > 0 && (av.iso || !use_a) && (bv.iso || !use_b);
     const size_t zs = gb_type_size(zcode);
-    gb_mat_result T;
-    T.nrows = nr;
-    T.ncols = nc;
-    T.tcode = zcode;
-    T.nvals = nvT;
-    T.iso = t_iso;
-    T.rowptr = gb_malloc_n<int64_t>(nr + 1);
-    T.colidx = gb_malloc_n<int32_t>(std::max<int64_t>(nvT, 1));
-    T.vals = gb_malloc(std::max<int64_t>(t_iso ? 1 : nvT, 1) * zs);
     if (nvT == 0) {
-        gb_memset(T.rowptr, 0, (nr + 1) * sizeof(int64_t));
+        gb_mat_result T = gb_empty_mat_result(nr, nc, zcode);
         gb_writeback_matrix(C, T, M, d, accum);
         return;
     }
+    gb_mat_result T = gb_new_mat_result(nr, nc, zcode, nvT, t_iso);
     gb_scratch s;
     const void *xa = use_a ? gb_view_vals_as(av, xcode, s) : nullptr;
     const void *xb = use_b ? gb_view_vals_as(bv, xcode, s) : nullptr;
-    hipLaunchKernelGGL(k_kron_rowptr, dim3(kron_grid((nr + 1 + 63) / 64)), dim3(KRON_BLOCK), 0, gb_stream(), nr, p,
-                       av.nvals, bv.nvals, av.rowptr, bv.rowptr, T.rowptr);
+    // launches count waves; the knob kron_grid caps the blocks (tests: few blocks, so that a
+    // wave runs through many chunks)
+    const int wpb = KRON_BLOCK / 64;
+    int64_t gcap = gb_knob("kron_grid");
+    if (gcap <= 0 || gcap > 8192) gcap = 8192;
+    hipLaunchKernelGGL(k_kron_rowptr, dim3(gb_grid((nr + 1 + 63) / 64, wpb, gcap)), dim3(KRON_BLOCK), 0, gb_stream(),
+                       nr, p, av.nvals, bv.nvals, av.rowptr, bv.rowptr, T.rowptr);
     GB_LAUNCH_CHECK();
     const bool rows = gb_knob("kron_method") == 1;
     // a wave takes a run of chunks (4 or more, once there are that many)
-    const unsigned grid = rows ? kron_grid((nr + 63) / 64) : kron_grid(((nvT + KRON_CHUNK - 1) / KRON_CHUNK + 3) / 4);
+    const unsigned grid = gb_grid(rows ? (nr + 63) / 64 : ((nvT + KRON_CHUNK - 1) / KRON_CHUNK + 3) / 4, wpb, gcap);
     auto fill = [&](auto vop) {
         using V = decltype(vop);
         if (rows)
@@ -366,7 +290,7 @@ void gb_kronecker(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_BinaryOp op, GB_
     };
     const bool moves = (opc == GBAMD_OP_FIRST || opc == GBAMD_OP_SECOND || opc == GBAMD_OP_ANY) && xcode == zcode;
     if (t_iso) {
-        kron_dispatch_xz(xcode, zcode, [&](auto x, auto z) {
+        gb_dispatch_xz(xcode, zcode, [&](auto x, auto z) {
             using X = decltype(x);
             using Z = decltype(z);
             hipLaunchKernelGGL((k_kron_iso<X, Z>), dim3(1), dim3(1), 0, gb_stream(), opc, (const X *)xa,
@@ -376,14 +300,9 @@ void gb_kronecker(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_BinaryOp op, GB_
     } else if (moves) {
         const bool from_b = opc != GBAMD_OP_FIRST;
         const void *src = from_b ? xb : xa;
-        switch ((int)zs) {
-        case 1: fill(kron_move<1>{src, from_b, T.vals}); break;
-        case 2: fill(kron_move<2>{src, from_b, T.vals}); break;
-        case 4: fill(kron_move<4>{src, from_b, T.vals}); break;
-        default: fill(kron_move<8>{src, from_b, T.vals}); break;
-        }
+        gb_with_size(zs, [&](auto w) { fill(kron_move<(int)sizeof(w)>{src, from_b, T.vals}); });
     } else {
-        kron_dispatch_xz(xcode, zcode, [&](auto x, auto z) {
+        gb_dispatch_xz(xcode, zcode, [&](auto x, auto z) {
             using X = decltype(x);
             using Z = decltype(z);
             fill(kron_compute<X, Z>{opc, (const X *)xa, (const X *)xb, av.iso, bv.iso, use_a, use_b, (Z *)T.vals});

@@ -26,23 +26,7 @@
 #include "gb_internal.h"
 
 #define MXM_BLOCK 256
-static inline unsigned mxm_grid(int64_t n, unsigned cap = 16384) {
-    int64_t g = (n + MXM_BLOCK - 1) / MXM_BLOCK;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
-}
-#define MXM_STRIDE(i, n) \
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-__global__ void k_rowof(const int64_t *__restrict__ rowptr, int64_t r0, int64_t r1, int64_t pbase,
-                        int64_t *__restrict__ rowof) {
-    int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
-    int lane = threadIdx.x & 63;
-    int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t i = r0 + wave; i < r1; i += nw)
-        for (int64_t p = rowptr[i] + lane; p < rowptr[i + 1]; p += 64) rowof[p - pbase] = i;
-}
+#define MXM_GRID_CAP 16384  // blocks of every launch here
 
 // ================================================================== masked dot
 template <class SR, class X, class Z>
@@ -51,7 +35,7 @@ __global__ __launch_bounds__(MXM_BLOCK) void k_dot_masked(
     const int64_t *__restrict__ arp, const int32_t *__restrict__ aci, const X *__restrict__ avx, bool a_iso,
     const int64_t *__restrict__ brp, const int32_t *__restrict__ bci, const X *__restrict__ bvx, bool b_iso,
     Z *__restrict__ tval, uint8_t *__restrict__ tflag) {
-    MXM_STRIDE(q, nm) {
+    GB_GRID_LOOP(q, nm) {
         const int64_t i = mrowof[q];
         const int32_t j = mci[q];
         const int64_t pa0 = arp[i], ea = arp[i + 1], pb0 = brp[j], eb = brp[j + 1];
@@ -211,14 +195,14 @@ static bool exact_monoid(int mon, int zcode) {
 
 __global__ void k_gather_rowptr(const int64_t *__restrict__ mrp, const int64_t *__restrict__ pos, int64_t nrows,
                                 int64_t *__restrict__ trp) {
-    MXM_STRIDE(i, nrows + 1) trp[i] = pos[mrp[i]];
+    GB_GRID_LOOP(i, nrows + 1) trp[i] = pos[mrp[i]];
 }
 
 template <class Z>
 __global__ void k_compact_dot(int64_t nm, const uint8_t *__restrict__ flag, const int64_t *__restrict__ pos,
                               const int32_t *__restrict__ mci, const Z *__restrict__ tval, int32_t *__restrict__ oci,
                               Z *__restrict__ ovx) {
-    MXM_STRIDE(q, nm) {
+    GB_GRID_LOOP(q, nm) {
         if (flag[q]) {
             int64_t o = pos[q];
             oci[o] = mci[q];
@@ -246,7 +230,7 @@ __global__ void k_row_flops(const int64_t *__restrict__ arp, const int32_t *__re
 
 __global__ void k_entry_counts(const int32_t *__restrict__ aci, int64_t p0, int64_t np, const int64_t *__restrict__ brp,
                                int64_t *__restrict__ cnt) {
-    MXM_STRIDE(q, np) {
+    GB_GRID_LOOP(q, np) {
         int32_t k = aci[p0 + q];
         cnt[q] = brp[k + 1] - brp[k];
     }
@@ -283,14 +267,14 @@ __global__ __launch_bounds__(MXM_BLOCK) void k_expand(
 }
 
 __global__ void k_run_heads(const uint64_t *__restrict__ keys, int64_t n, int64_t *__restrict__ head) {
-    MXM_STRIDE(q, n) head[q] = (q == 0 || keys[q] != keys[q - 1]) ? 1 : 0;
+    GB_GRID_LOOP(q, n) head[q] = (q == 0 || keys[q] != keys[q - 1]) ? 1 : 0;
 }
 
 template <class SR, class Z>
 __global__ void k_fold(SR sr, const uint64_t *__restrict__ keys, const int64_t *__restrict__ perm,
                        const int64_t *__restrict__ pos, int64_t n, const Z *__restrict__ vals, int64_t r0,
                        unsigned long long *__restrict__ rowcnt, int32_t *__restrict__ oci, Z *__restrict__ ovx) {
-    MXM_STRIDE(q, n) {
+    GB_GRID_LOOP(q, n) {
         if (q != 0 && keys[q] == keys[q - 1]) continue;
         int64_t o = pos[q];
         oci[o] = (int32_t)(keys[q] & 0xffffffffULL);
@@ -348,8 +332,7 @@ void gb_spgemm(gb_mat_result &T, gb_csr_view &A, gb_csr_view &B, gb_csr_view *BT
         int64_t *mrowof = nullptr;
         auto rowof = [&]() {
             mrowof = s.get<int64_t>(nm);
-            hipLaunchKernelGGL(k_rowof, dim3(mxm_grid(std::min<int64_t>(nrows * 64, 1LL << 22))), dim3(MXM_BLOCK), 0,
-                               gb_stream(), mask.rowptr, (int64_t)0, nrows, (int64_t)0, mrowof);
+            gb_rows_of(mask.rowptr, 0, nrows, 0, mrowof, MXM_GRID_CAP);
         };
         gb_dispatch_sr(info, [&](auto srf, auto x, auto z) {
             using SRT = decltype(srf);
@@ -370,7 +353,7 @@ void gb_spgemm(gb_mat_result &T, gb_csr_view &A, gb_csr_view &B, gb_csr_view *BT
                 const int64_t nh = gb_dot_two_sided(A, *BT, mask, info, av, btv, tval, flag, &hq);
                 if (nh) {
                     rowof();
-                    const unsigned g = mxm_grid(std::min<int64_t>(nh * 64, 1LL << 24));
+                    const unsigned g = gb_grid(std::min<int64_t>(nh * 64, 1LL << 24), MXM_BLOCK, MXM_GRID_CAP);
                     hipLaunchKernelGGL((k_dot_masked_group<SRT, X, Z, 64>), dim3(g), dim3(MXM_BLOCK), 0, gb_stream(),
                                        srf, nh, mrowof, mask.colidx, A.rowptr, A.colidx, (const X *)av, A.iso,
                                        BT->rowptr, BT->colidx, (const X *)btv, BT->iso, (Z *)tval, flag, hq);
@@ -379,7 +362,7 @@ void gb_spgemm(gb_mat_result &T, gb_csr_view &A, gb_csr_view &B, gb_csr_view *BT
                 }
             } else if (nm && gsel > 1 && exact) {
                 rowof();
-                const unsigned g = mxm_grid(std::min<int64_t>(nm * gsel, 1LL << 24));
+                const unsigned g = gb_grid(std::min<int64_t>(nm * gsel, 1LL << 24), MXM_BLOCK, MXM_GRID_CAP);
 #define GB_DOT_GROUP(GG)                                                                                 \
     hipLaunchKernelGGL((k_dot_masked_group<SRT, X, Z, GG>), dim3(g), dim3(MXM_BLOCK), 0, gb_stream(), srf, nm, \
                        mrowof, mask.colidx, A.rowptr, A.colidx, (const X *)av, A.iso, BT->rowptr, BT->colidx, \
@@ -392,21 +375,23 @@ void gb_spgemm(gb_mat_result &T, gb_csr_view &A, gb_csr_view &B, gb_csr_view *BT
 #undef GB_DOT_GROUP
             } else if (nm) {
                 rowof();
-                hipLaunchKernelGGL((k_dot_masked<SRT, X, Z>), dim3(mxm_grid(nm)), dim3(MXM_BLOCK), 0, gb_stream(),
-                                   srf, nm, mrowof, mask.colidx, A.rowptr, A.colidx, (const X *)av, A.iso,
-                                   BT->rowptr, BT->colidx, (const X *)btv, BT->iso, (Z *)tval, flag);
+                hipLaunchKernelGGL((k_dot_masked<SRT, X, Z>), dim3(gb_grid(nm, MXM_BLOCK, MXM_GRID_CAP)),
+                                   dim3(MXM_BLOCK), 0, gb_stream(), srf, nm, mrowof, mask.colidx, A.rowptr, A.colidx,
+                                   (const X *)av, A.iso, BT->rowptr, BT->colidx, (const X *)btv, BT->iso, (Z *)tval,
+                                   flag);
             }
             GB_LAUNCH_CHECK();
             gb_exclusive_scan_u8(flag, pos, nm);
             int64_t nz = gb_read_i64(pos + nm);
             T.rowptr = gb_malloc_n<int64_t>(nrows + 1);
-            hipLaunchKernelGGL(k_gather_rowptr, dim3(mxm_grid(nrows + 1)), dim3(MXM_BLOCK), 0, gb_stream(),
-                               mask.rowptr, pos, nrows, T.rowptr);
+            hipLaunchKernelGGL(k_gather_rowptr, dim3(gb_grid(nrows + 1, MXM_BLOCK, MXM_GRID_CAP)), dim3(MXM_BLOCK), 0,
+                               gb_stream(), mask.rowptr, pos, nrows, T.rowptr);
             T.colidx = gb_malloc_n<int32_t>(nz);
             T.vals = gb_malloc((iso ? 1 : nz) * zs);
             if (nm)
-                hipLaunchKernelGGL(k_compact_dot<Z>, dim3(mxm_grid(nm)), dim3(MXM_BLOCK), 0, gb_stream(), nm, flag,
-                                   pos, mask.colidx, (const Z *)tval, T.colidx, iso ? nullptr : (Z *)T.vals);
+                hipLaunchKernelGGL(k_compact_dot<Z>, dim3(gb_grid(nm, MXM_BLOCK, MXM_GRID_CAP)), dim3(MXM_BLOCK), 0,
+                                   gb_stream(), nm, flag, pos, mask.colidx, (const Z *)tval, T.colidx,
+                                   iso ? nullptr : (Z *)T.vals);
             if (iso)
                 hipLaunchKernelGGL((k_iso_value2<SRT, X, Z>), dim3(1), dim3(1), 0, gb_stream(), srf, (const X *)av,
                                    (const X *)btv, (Z *)T.vals);
@@ -422,8 +407,9 @@ void gb_spgemm(gb_mat_result &T, gb_csr_view &A, gb_csr_view &B, gb_csr_view *BT
     int64_t *fl = s.get<int64_t>(nrows + 1);
     int64_t *flp = s.get<int64_t>(nrows + 1);
     if (nrows)
-        hipLaunchKernelGGL(k_row_flops, dim3(mxm_grid(std::min<int64_t>(nrows * 64, 1LL << 22))), dim3(MXM_BLOCK), 0,
-                           gb_stream(), A.rowptr, A.colidx, nrows, B.rowptr, fl);
+        hipLaunchKernelGGL(k_row_flops,
+                           dim3(gb_grid(std::min<int64_t>(nrows * 64, 1LL << 22), MXM_BLOCK, MXM_GRID_CAP)),
+                           dim3(MXM_BLOCK), 0, gb_stream(), A.rowptr, A.colidx, nrows, B.rowptr, fl);
     GB_LAUNCH_CHECK();
     if (gb_knob("spgemm_method") != 1) {
         // default: hash Gustavson (gb_spgemm_hash.hip)
@@ -483,11 +469,10 @@ void gb_spgemm(gb_mat_result &T, gb_csr_view &A, gb_csr_view &B, gb_csr_view *BT
             int64_t *eoff = cs.get<int64_t>(np + 1);
             int64_t *rowof = cs.get<int64_t>(np);
             if (np) {
-                hipLaunchKernelGGL(k_entry_counts, dim3(mxm_grid(np)), dim3(MXM_BLOCK), 0, gb_stream(), A.colidx, p0,
-                                   np, B.rowptr, cnt);
-                hipLaunchKernelGGL(k_rowof, dim3(mxm_grid(std::min<int64_t>((r1 - r0) * 64, 1LL << 22))),
-                                   dim3(MXM_BLOCK), 0, gb_stream(), A.rowptr, r0, r1, p0, rowof);
+                hipLaunchKernelGGL(k_entry_counts, dim3(gb_grid(np, MXM_BLOCK, MXM_GRID_CAP)), dim3(MXM_BLOCK), 0,
+                                   gb_stream(), A.colidx, p0, np, B.rowptr, cnt);
                 GB_LAUNCH_CHECK();
+                gb_rows_of(A.rowptr, r0, r1, p0, rowof, MXM_GRID_CAP);
             }
             gb_exclusive_scan_i64(cnt, eoff, np);
             const int64_t fc = gb_read_i64(eoff + np);
@@ -500,7 +485,8 @@ void gb_spgemm(gb_mat_result &T, gb_csr_view &A, gb_csr_view &B, gb_csr_view *BT
             uint64_t *keys = cs.get<uint64_t>(fc);
             int64_t *perm = cs.get<int64_t>(fc);
             Z *vals = iso ? nullptr : cs.get<Z>(fc);
-            hipLaunchKernelGGL((k_expand<SRT, X, Z>), dim3(mxm_grid(std::min<int64_t>(np * 64, 1LL << 24))),
+            hipLaunchKernelGGL((k_expand<SRT, X, Z>),
+                               dim3(gb_grid(std::min<int64_t>(np * 64, 1LL << 24), MXM_BLOCK, MXM_GRID_CAP)),
                                dim3(MXM_BLOCK), 0, gb_stream(), srf, p0, np, r0, rowof, A.colidx, (const X *)av, A.iso,
                                B.rowptr, B.colidx, (const X *)bv, B.iso, eoff, keys, perm, vals);
             GB_LAUNCH_CHECK();
@@ -509,14 +495,15 @@ void gb_spgemm(gb_mat_result &T, gb_csr_view &A, gb_csr_view &B, gb_csr_view *BT
             gb_sort_pairs_u64(keys, perm, fc, 32 + rbits);
             int64_t *head = cs.get<int64_t>(fc);
             int64_t *pos = cs.get<int64_t>(fc + 1);
-            hipLaunchKernelGGL(k_run_heads, dim3(mxm_grid(fc)), dim3(MXM_BLOCK), 0, gb_stream(), keys, fc, head);
+            hipLaunchKernelGGL(k_run_heads, dim3(gb_grid(fc, MXM_BLOCK, MXM_GRID_CAP)), dim3(MXM_BLOCK), 0, gb_stream(),
+                               keys, fc, head);
             GB_LAUNCH_CHECK();
             gb_exclusive_scan_i64(head, pos, fc);
             const int64_t nu = gb_read_i64(pos + fc);
             int32_t *oci = gb_malloc_n<int32_t>(nu);
             Z *ovx = iso ? nullptr : gb_malloc_n<Z>(nu);
-            hipLaunchKernelGGL((k_fold<SRT, Z>), dim3(mxm_grid(fc)), dim3(MXM_BLOCK), 0, gb_stream(), srf, keys, perm,
-                               pos, fc, (const Z *)vals, r0, rowcnt, oci, ovx);
+            hipLaunchKernelGGL((k_fold<SRT, Z>), dim3(gb_grid(fc, MXM_BLOCK, MXM_GRID_CAP)), dim3(MXM_BLOCK), 0,
+                               gb_stream(), srf, keys, perm, pos, fc, (const Z *)vals, r0, rowcnt, oci, ovx);
             GB_LAUNCH_CHECK();
             chunk_nz.push_back(nu);
             chunk_ci.push_back(oci);

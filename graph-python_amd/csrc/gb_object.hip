@@ -9,38 +9,13 @@
 #include <algorithm>
 #include <vector>
 
-#include "gb_device.cuh"
 #include <mutex>
 
+#include "gb_dispatch.cuh"
 #include "gb_internal.h"
 
 #define GB_BLOCK 256
-static inline unsigned grid_for(int64_t n, unsigned cap = 8192) {
-    int64_t g = (n + GB_BLOCK - 1) / GB_BLOCK;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
-}
-#define GRID_STRIDE(i, n) \
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-// dispatch a functor templated on the C type of a type code
-template <class F>
-static void with_type(int code, F &&f) {
-    switch (code) {
-    case GBAMD_T_BOOL: f((bool)0); break;
-    case GBAMD_T_INT8: f((int8_t)0); break;
-    case GBAMD_T_UINT8: f((uint8_t)0); break;
-    case GBAMD_T_INT16: f((int16_t)0); break;
-    case GBAMD_T_UINT16: f((uint16_t)0); break;
-    case GBAMD_T_INT32: f((int32_t)0); break;
-    case GBAMD_T_UINT32: f((uint32_t)0); break;
-    case GBAMD_T_INT64: f((int64_t)0); break;
-    case GBAMD_T_UINT64: f((uint64_t)0); break;
-    case GBAMD_T_FP32: f((float)0); break;
-    default: f((double)0); break;
-    }
-}
+#define OBJ_GRID_CAP 8192  // blocks of every launch here
 
 // ================================================================== object basics
 GB_Obj *gb_obj_check(const void *p, bool allow_null) {
@@ -413,7 +388,7 @@ __global__ void k_check_and_key(const uint64_t *__restrict__ I, const uint64_t *
                                 int64_t n, uint64_t nrows, uint64_t ncols,
                                 uint64_t *__restrict__ keys, int64_t *__restrict__ perm,
                                 int *__restrict__ bad) {
-    GRID_STRIDE(q, n) {
+    GB_GRID_LOOP(q, n) {
         uint64_t i = I[q], j = J ? J[q] : 0;
         if (i >= nrows || j >= ncols) {
             *bad = 1;
@@ -426,7 +401,7 @@ __global__ void k_check_and_key(const uint64_t *__restrict__ I, const uint64_t *
 }
 
 __global__ void k_heads(const uint64_t *__restrict__ keys, int64_t n, int64_t *__restrict__ head) {
-    GRID_STRIDE(q, n) head[q] = (q == 0 || keys[q] != keys[q - 1]) ? 1 : 0;
+    GB_GRID_LOOP(q, n) head[q] = (q == 0 || keys[q] != keys[q - 1]) ? 1 : 0;
 }
 
 // one thread per run: fold duplicates in input order with the dup operator
@@ -435,7 +410,7 @@ template <class T>
 __global__ void k_fold_runs(const uint64_t *__restrict__ keys, const int64_t *__restrict__ perm,
                             const int64_t *__restrict__ pos, int64_t n, const T *__restrict__ X,
                             bool x_iso, int dup, uint64_t *__restrict__ ukeys, T *__restrict__ uvals) {
-    GRID_STRIDE(q, n) {
+    GB_GRID_LOOP(q, n) {
         if (q != 0 && keys[q] == keys[q - 1]) continue;
         T v = X[x_iso ? 0 : perm[q]];
         int64_t r = q + 1;
@@ -451,7 +426,7 @@ __global__ void k_fold_runs(const uint64_t *__restrict__ keys, const int64_t *__
 
 __global__ void k_rows_hist(const uint64_t *__restrict__ ukeys, int64_t nu,
                             unsigned long long *__restrict__ cnt, int32_t *__restrict__ colidx) {
-    GRID_STRIDE(q, nu) {
+    GB_GRID_LOOP(q, nu) {
         atomicAdd(&cnt[ukeys[q] >> 32], 1ULL);
         colidx[q] = (int32_t)(ukeys[q] & 0xffffffffULL);
     }
@@ -460,7 +435,7 @@ __global__ void k_rows_hist(const uint64_t *__restrict__ ukeys, int64_t nu,
 template <class T>
 __global__ void k_scatter_vec(const uint64_t *__restrict__ ukeys, const T *__restrict__ uvals,
                               int64_t nu, unsigned long long *__restrict__ bits, T *__restrict__ dense) {
-    GRID_STRIDE(q, nu) {
+    GB_GRID_LOOP(q, nu) {
         uint64_t i = ukeys[q] >> 32;
         atomicOr(&bits[i >> 6], 1ULL << (i & 63));
         if (dense) dense[i] = uvals[q];
@@ -480,8 +455,8 @@ static void coo_sort_fold(const GrB_Index *I, const GrB_Index *J, const void *X_
     int64_t *perm = s.get<int64_t>(n);
     int *bad = s.get<int>(1);
     gb_memset(bad, 0, sizeof(int));
-    hipLaunchKernelGGL(k_check_and_key, dim3(grid_for(n)), dim3(GB_BLOCK), 0, gb_stream(), dI, dJ, n,
-                       (uint64_t)nrows, (uint64_t)ncols, keys, perm, bad);
+    hipLaunchKernelGGL(k_check_and_key, dim3(gb_grid(n, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0, gb_stream(), dI,
+                       dJ, n, (uint64_t)nrows, (uint64_t)ncols, keys, perm, bad);
     GB_LAUNCH_CHECK();
     int hbad = 0;
     gb_copy_d2h(&hbad, bad, sizeof(int));
@@ -490,16 +465,17 @@ static void coo_sort_fold(const GrB_Index *I, const GrB_Index *J, const void *X_
     while (rbits < 31 && (1LL << rbits) < nrows) rbits++;
     gb_sort_pairs_u64(keys, perm, n, 32 + rbits);
     int64_t *head = s.get<int64_t>(n), *pos = s.get<int64_t>(n + 1);
-    hipLaunchKernelGGL(k_heads, dim3(grid_for(n)), dim3(GB_BLOCK), 0, gb_stream(), keys, n, head);
+    hipLaunchKernelGGL(k_heads, dim3(gb_grid(n, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0, gb_stream(), keys, n,
+                       head);
     GB_LAUNCH_CHECK();
     gb_exclusive_scan_i64(head, pos, n);
     int64_t nu = gb_read_i64(pos + n);
     uint64_t *ukeys = gb_malloc_n<uint64_t>(nu);
     void *uvals = X_dev ? gb_malloc(nu * gb_type_size(code)) : nullptr;
-    with_type(code, [&](auto z) {
+    gb_with_type(code, [&](auto z) {
         using T = decltype(z);
-        hipLaunchKernelGGL(k_fold_runs<T>, dim3(grid_for(n)), dim3(GB_BLOCK), 0, gb_stream(), keys, perm,
-                           pos, n, (const T *)X_dev, x_iso, dup_opcode, ukeys, (T *)uvals);
+        hipLaunchKernelGGL(k_fold_runs<T>, dim3(gb_grid(n, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0, gb_stream(),
+                           keys, perm, pos, n, (const T *)X_dev, x_iso, dup_opcode, ukeys, (T *)uvals);
     });
     GB_LAUNCH_CHECK();
     *ukeys_out = ukeys;
@@ -546,8 +522,8 @@ void gb_build(GB_Obj *C, const GrB_Index *I, const GrB_Index *J, const void *X, 
         int64_t *cnt = s.get<int64_t>(C->nrows + 1);
         gb_memset(cnt, 0, (C->nrows + 1) * sizeof(int64_t));
         int32_t *colidx = gb_malloc_n<int32_t>(nu);
-        hipLaunchKernelGGL(k_rows_hist, dim3(grid_for(nu)), dim3(GB_BLOCK), 0, gb_stream(), ukeys, nu,
-                           (unsigned long long *)cnt, colidx);
+        hipLaunchKernelGGL(k_rows_hist, dim3(gb_grid(nu, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0, gb_stream(),
+                           ukeys, nu, (unsigned long long *)cnt, colidx);
         GB_LAUNCH_CHECK();
         int64_t *rowptr = gb_malloc_n<int64_t>(C->nrows + 1);
         gb_exclusive_scan_i64(cnt, rowptr, C->nrows);
@@ -558,10 +534,11 @@ void gb_build(GB_Obj *C, const GrB_Index *I, const GrB_Index *J, const void *X, 
         uint64_t *bits = gb_malloc_n<uint64_t>(nw);
         gb_memset(bits, 0, nw * sizeof(uint64_t));
         void *dense = x_iso ? uvals : gb_malloc(C->nrows * ts);
-        with_type(code, [&](auto z) {
+        gb_with_type(code, [&](auto z) {
             using T = decltype(z);
-            hipLaunchKernelGGL(k_scatter_vec<T>, dim3(grid_for(nu)), dim3(GB_BLOCK), 0, gb_stream(), ukeys,
-                               (const T *)uvals, nu, (unsigned long long *)bits, x_iso ? nullptr : (T *)dense);
+            hipLaunchKernelGGL(k_scatter_vec<T>, dim3(gb_grid(nu, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0,
+                               gb_stream(), ukeys, (const T *)uvals, nu, (unsigned long long *)bits,
+                               x_iso ? nullptr : (T *)dense);
         });
         GB_LAUNCH_CHECK();
         gb_free(ukeys);
@@ -576,24 +553,17 @@ void gb_build(GB_Obj *C, const GrB_Index *I, const GrB_Index *J, const void *X, 
 }
 
 // ================================================================== extract
-__global__ void k_rows_of(const int64_t *__restrict__ rowptr, int64_t nrows, uint64_t *__restrict__ I) {
-    int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
-    int lane = threadIdx.x & 63;
-    int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t i = wave; i < nrows; i += nw)
-        for (int64_t p = rowptr[i] + lane; p < rowptr[i + 1]; p += 64) I[p] = (uint64_t)i;
-}
 __global__ void k_i32_to_u64(const int32_t *__restrict__ a, int64_t n, uint64_t *__restrict__ b) {
-    GRID_STRIDE(q, n) b[q] = (uint64_t)(uint32_t)a[q];
+    GB_GRID_LOOP(q, n) b[q] = (uint64_t)(uint32_t)a[q];
 }
 __global__ void k_word_pop2(const uint64_t *__restrict__ bits, int64_t nw, int64_t *__restrict__ pop) {
-    GRID_STRIDE(w, nw) pop[w] = __popcll(bits[w]);
+    GB_GRID_LOOP(w, nw) pop[w] = __popcll(bits[w]);
 }
 template <class T>
 __global__ void k_bitmap_compact(const uint64_t *__restrict__ bits, const T *__restrict__ dense, bool iso,
                                  int64_t n, const int64_t *__restrict__ woff, uint64_t *__restrict__ idx,
                                  T *__restrict__ vals) {
-    GRID_STRIDE(i, n) {
+    GB_GRID_LOOP(i, n) {
         uint64_t w = bits[i >> 6];
         int b = i & 63;
         if ((w >> b) & 1ULL) {
@@ -634,15 +604,13 @@ void gb_extract_tuples(GB_Obj *A, GrB_Index *I, GrB_Index *J, void *X, int xcode
     if (A->kind == GB_KIND_MATRIX) {
         if (I) {
             uint64_t *dI = s.get<uint64_t>(nz);
-            hipLaunchKernelGGL(k_rows_of, dim3(grid_for(A->nrows * 64)), dim3(GB_BLOCK), 0, gb_stream(),
-                               A->rowptr, A->nrows, dI);
-            GB_LAUNCH_CHECK();
+            gb_rows_of(A->rowptr, 0, A->nrows, 0, (int64_t *)dI, OBJ_GRID_CAP);  // a row >= 0 is the same bits
             gb_copy_d2h(I, dI, nz * sizeof(uint64_t));
         }
         if (J) {
             uint64_t *dJ = s.get<uint64_t>(nz);
-            hipLaunchKernelGGL(k_i32_to_u64, dim3(grid_for(nz)), dim3(GB_BLOCK), 0, gb_stream(), A->colidx,
-                               nz, dJ);
+            hipLaunchKernelGGL(k_i32_to_u64, dim3(gb_grid(nz, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0, gb_stream(),
+                               A->colidx, nz, dJ);
             GB_LAUNCH_CHECK();
             gb_copy_d2h(J, dJ, nz * sizeof(uint64_t));
         }
@@ -651,15 +619,16 @@ void gb_extract_tuples(GB_Obj *A, GrB_Index *I, GrB_Index *J, void *X, int xcode
     }
     int64_t n = A->nrows, nw = gb_words(n);
     int64_t *pop = s.get<int64_t>(nw), *woff = s.get<int64_t>(nw + 1);
-    hipLaunchKernelGGL(k_word_pop2, dim3(grid_for(nw)), dim3(GB_BLOCK), 0, gb_stream(), A->bits, nw, pop);
+    hipLaunchKernelGGL(k_word_pop2, dim3(gb_grid(nw, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0, gb_stream(), A->bits,
+                       nw, pop);
     GB_LAUNCH_CHECK();
     gb_exclusive_scan_i64(pop, woff, nw);
     uint64_t *dI = s.get<uint64_t>(nz);
     void *dX = (X && !A->iso) ? s.get<char>(nz * A->type->size) : nullptr;
-    with_type(A->type->code, [&](auto z) {
+    gb_with_type(A->type->code, [&](auto z) {
         using T = decltype(z);
-        hipLaunchKernelGGL(k_bitmap_compact<T>, dim3(grid_for(n)), dim3(GB_BLOCK), 0, gb_stream(), A->bits,
-                           (const T *)A->dense, A->iso, n, woff, dI, (T *)dX);
+        hipLaunchKernelGGL(k_bitmap_compact<T>, dim3(gb_grid(n, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0,
+                           gb_stream(), A->bits, (const T *)A->dense, A->iso, n, woff, dI, (T *)dX);
     });
     GB_LAUNCH_CHECK();
     if (I) gb_copy_d2h(I, dI, nz * sizeof(uint64_t));
@@ -688,7 +657,7 @@ template <class T>
 __global__ void k_insert(const int64_t *__restrict__ rp, const int32_t *__restrict__ ci, const T *__restrict__ vx,
                          int64_t nrows, int64_t nvals, int64_t row, int64_t pos, int32_t col, T val,
                          int64_t *__restrict__ rp2, int32_t *__restrict__ ci2, T *__restrict__ vx2) {
-    GRID_STRIDE(q, nvals + 1) {
+    GB_GRID_LOOP(q, nvals + 1) {
         if (q < pos) {
             ci2[q] = ci[q];
             vx2[q] = vx[q];
@@ -700,19 +669,19 @@ __global__ void k_insert(const int64_t *__restrict__ rp, const int32_t *__restri
             vx2[q] = vx[q - 1];
         }
     }
-    GRID_STRIDE(r, nrows + 1) rp2[r] = rp[r] + (r > row ? 1 : 0);
+    GB_GRID_LOOP(r, nrows + 1) rp2[r] = rp[r] + (r > row ? 1 : 0);
 }
 
 template <class T>
 __global__ void k_delete(const int64_t *__restrict__ rp, const int32_t *__restrict__ ci, const T *__restrict__ vx,
                          int64_t nrows, int64_t nvals, int64_t row, int64_t pos, int64_t *__restrict__ rp2,
                          int32_t *__restrict__ ci2, T *__restrict__ vx2, bool iso) {
-    GRID_STRIDE(q, nvals - 1) {
+    GB_GRID_LOOP(q, nvals - 1) {
         int64_t src = q < pos ? q : q + 1;
         ci2[q] = ci[src];
         if (!iso) vx2[q] = vx[src];
     }
-    GRID_STRIDE(r, nrows + 1) rp2[r] = rp[r] - (r > row ? 1 : 0);
+    GB_GRID_LOOP(r, nrows + 1) rp2[r] = rp[r] - (r > row ? 1 : 0);
 }
 
 static void matrix_de_iso(GB_Obj *A) {
@@ -759,9 +728,9 @@ static void matrix_set_element(GB_Obj *A, T x, int64_t i, int64_t j) {
     int32_t *ci2 = gb_malloc_n<int32_t>(nz + 1);
     T *vx2 = gb_malloc_n<T>(nz + 1);
     const T *vx = (const T *)(A->vals ? A->vals : (void *)vx2);
-    hipLaunchKernelGGL(k_insert<T>, dim3(grid_for(std::max(nz + 1, A->nrows + 1))), dim3(GB_BLOCK), 0, gb_stream(),
-                       A->rowptr, A->colidx ? A->colidx : ci2, vx, A->nrows, nz, i, h[0], (int32_t)j, x, rp2,
-                       ci2, vx2);
+    hipLaunchKernelGGL(k_insert<T>, dim3(gb_grid(std::max(nz + 1, A->nrows + 1), GB_BLOCK, OBJ_GRID_CAP)),
+                       dim3(GB_BLOCK), 0, gb_stream(), A->rowptr, A->colidx ? A->colidx : ci2, vx, A->nrows, nz, i,
+                       h[0], (int32_t)j, x, rp2, ci2, vx2);
     GB_LAUNCH_CHECK();
     gb_sync();
     gb_install_csr(A, A->nrows, A->ncols, nz + 1, rp2, ci2, vx2, false);
@@ -834,7 +803,7 @@ static GrB_Info vector_extract_element(T *x, GB_Obj *v, int64_t i) {
     char buf[16];
     int code = v->type->code;
     gb_copy_d2h(buf, (const char *)v->dense + (v->iso ? 0 : i * v->type->size), v->type->size);
-    with_type(code, [&](auto z) {
+    gb_with_type(code, [&](auto z) {
         using S = decltype(z);
         S sv;
         memcpy(&sv, buf, sizeof(S));
@@ -856,7 +825,7 @@ static GrB_Info matrix_extract_element(T *x, GB_Obj *A, int64_t i, int64_t j) {
     if (!h[1]) return GrB_NO_VALUE;
     char buf[16];
     gb_copy_d2h(buf, (const char *)A->vals + (A->iso ? 0 : h[0] * A->type->size), A->type->size);
-    with_type(A->type->code, [&](auto z) {
+    gb_with_type(A->type->code, [&](auto z) {
         using S = decltype(z);
         S sv;
         memcpy(&sv, buf, sizeof(S));
@@ -880,11 +849,11 @@ static void matrix_remove_element(GB_Obj *A, int64_t i, int64_t j) {
     size_t ts = A->type->size;
     void *vx2 = A->iso ? gb_malloc(ts) : gb_malloc((nz - 1) * ts);
     if (A->iso) gb_copy_d2d(vx2, A->vals, ts);
-    with_type(A->type->code, [&](auto z) {
+    gb_with_type(A->type->code, [&](auto z) {
         using T = decltype(z);
-        hipLaunchKernelGGL(k_delete<T>, dim3(grid_for(std::max(nz, A->nrows + 1))), dim3(GB_BLOCK), 0, gb_stream(),
-                           A->rowptr, A->colidx, (const T *)A->vals, A->nrows, nz, i, h[0], rp2, ci2, (T *)vx2,
-                           A->iso);
+        hipLaunchKernelGGL(k_delete<T>, dim3(gb_grid(std::max(nz, A->nrows + 1), GB_BLOCK, OBJ_GRID_CAP)),
+                           dim3(GB_BLOCK), 0, gb_stream(), A->rowptr, A->colidx, (const T *)A->vals, A->nrows, nz, i,
+                           h[0], rp2, ci2, (T *)vx2, A->iso);
     });
     GB_LAUNCH_CHECK();
     gb_install_csr(A, A->nrows, A->ncols, nz - 1, rp2, ci2, vx2, A->iso);
@@ -893,7 +862,7 @@ static void matrix_remove_element(GB_Obj *A, int64_t i, int64_t j) {
 // ================================================================== import / export
 __global__ void k_u64_to_i32_check(const uint64_t *__restrict__ a, int64_t n, uint64_t bound,
                                    int32_t *__restrict__ b, int *__restrict__ bad) {
-    GRID_STRIDE(q, n) {
+    GB_GRID_LOOP(q, n) {
         uint64_t x = a[q];
         if (x >= bound) {
             *bad = 1;
@@ -905,7 +874,7 @@ __global__ void k_u64_to_i32_check(const uint64_t *__restrict__ a, int64_t n, ui
 // rows must be strictly increasing in column index (sorted, no duplicates)
 __global__ void k_check_sorted(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ ci, int64_t nrows,
                                int *__restrict__ jumbled) {
-    GRID_STRIDE(i, nrows) {
+    GB_GRID_LOOP(i, nrows) {
         for (int64_t p = rowptr[i] + 1; p < rowptr[i + 1]; p++)
             if (ci[p] <= ci[p - 1]) {
                 *jumbled = 1;
@@ -924,10 +893,10 @@ static void import_csr(GB_Obj *A, const GrB_Index *Ap, const GrB_Index *Ai, cons
     int32_t *ci = gb_malloc_n<int32_t>(nvals);
     int *flags = s.get<int>(2);
     gb_memset(flags, 0, 2 * sizeof(int));
-    hipLaunchKernelGGL(k_u64_to_i32_check, dim3(grid_for(nvals)), dim3(GB_BLOCK), 0, gb_stream(), ai, nvals,
-                       (uint64_t)ncols, ci, flags);
-    hipLaunchKernelGGL(k_check_sorted, dim3(grid_for(nrows)), dim3(GB_BLOCK), 0, gb_stream(), rp, ci, nrows,
-                       flags + 1);
+    hipLaunchKernelGGL(k_u64_to_i32_check, dim3(gb_grid(nvals, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0, gb_stream(),
+                       ai, nvals, (uint64_t)ncols, ci, flags);
+    hipLaunchKernelGGL(k_check_sorted, dim3(gb_grid(nrows, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0, gb_stream(), rp,
+                       ci, nrows, flags + 1);
     GB_LAUNCH_CHECK();
     int h[2];
     gb_copy_d2h(h, flags, sizeof(h));
@@ -987,9 +956,7 @@ static void export_matrix(GB_Obj *A, GrB_Index *Ap, GrB_Index *Ai, void *Ax, int
     if (format == GrB_COO_FORMAT) {
         uint64_t *dI = s.get<uint64_t>(nz);
         if (nz) {
-            hipLaunchKernelGGL(k_rows_of, dim3(grid_for(v.nrows * 64)), dim3(GB_BLOCK), 0, gb_stream(), v.rowptr,
-                               v.nrows, dI);
-            GB_LAUNCH_CHECK();
+            gb_rows_of(v.rowptr, 0, v.nrows, 0, (int64_t *)dI, OBJ_GRID_CAP);
         }
         gb_copy_d2h(Ap, dI, nz * sizeof(uint64_t));
     } else {
@@ -997,7 +964,8 @@ static void export_matrix(GB_Obj *A, GrB_Index *Ap, GrB_Index *Ai, void *Ax, int
     }
     if (nz) {
         uint64_t *dJ = s.get<uint64_t>(nz);
-        hipLaunchKernelGGL(k_i32_to_u64, dim3(grid_for(nz)), dim3(GB_BLOCK), 0, gb_stream(), v.colidx, nz, dJ);
+        hipLaunchKernelGGL(k_i32_to_u64, dim3(gb_grid(nz, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0, gb_stream(),
+                           v.colidx, nz, dJ);
         GB_LAUNCH_CHECK();
         gb_copy_d2h(Ai, dJ, nz * sizeof(uint64_t));
         values_to_host(Ax, xcode, v.vals, A->type->code, v.iso, nz);
@@ -1010,7 +978,7 @@ static void export_matrix(GB_Obj *A, GrB_Index *Ap, GrB_Index *Ai, void *Ax, int
 // ================================================================== resize
 __global__ void k_resize_rows(const int64_t *__restrict__ rp, const int32_t *__restrict__ ci, int64_t nrows_keep,
                               int64_t ncols, int64_t *__restrict__ cnt) {
-    GRID_STRIDE(i, nrows_keep) {
+    GB_GRID_LOOP(i, nrows_keep) {
         int64_t c = 0;
         for (int64_t p = rp[i]; p < rp[i + 1]; p++) c += ci[p] < ncols;
         cnt[i] = c;
@@ -1020,7 +988,7 @@ template <class T>
 __global__ void k_resize_fill(const int64_t *__restrict__ rp, const int32_t *__restrict__ ci, const T *__restrict__ vx,
                               int64_t nrows_keep, int64_t ncols, const int64_t *__restrict__ rp2,
                               int32_t *__restrict__ ci2, T *__restrict__ vx2) {
-    GRID_STRIDE(i, nrows_keep) {
+    GB_GRID_LOOP(i, nrows_keep) {
         int64_t o = rp2[i];
         for (int64_t p = rp[i]; p < rp[i + 1]; p++)
             if (ci[p] < ncols) {
@@ -1038,8 +1006,8 @@ static void matrix_resize(GB_Obj *A, int64_t nrows, int64_t ncols) {
     int64_t *cnt = s.get<int64_t>(nrows + 1);
     gb_memset(cnt, 0, (nrows + 1) * sizeof(int64_t));
     if (keep && A->nvals) {
-        hipLaunchKernelGGL(k_resize_rows, dim3(grid_for(keep)), dim3(GB_BLOCK), 0, gb_stream(), A->rowptr,
-                           A->colidx, keep, ncols, cnt);
+        hipLaunchKernelGGL(k_resize_rows, dim3(gb_grid(keep, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0, gb_stream(),
+                           A->rowptr, A->colidx, keep, ncols, cnt);
         GB_LAUNCH_CHECK();
     }
     int64_t *rp2 = gb_malloc_n<int64_t>(nrows + 1);
@@ -1050,10 +1018,11 @@ static void matrix_resize(GB_Obj *A, int64_t nrows, int64_t ncols) {
     void *vx2 = A->iso ? gb_malloc(ts) : gb_malloc(nz * ts);
     if (A->iso) gb_copy_d2d(vx2, A->vals, ts);
     if (nz) {
-        with_type(A->type->code, [&](auto z) {
+        gb_with_type(A->type->code, [&](auto z) {
             using T = decltype(z);
-            hipLaunchKernelGGL(k_resize_fill<T>, dim3(grid_for(keep)), dim3(GB_BLOCK), 0, gb_stream(), A->rowptr,
-                               A->colidx, (const T *)A->vals, keep, ncols, rp2, ci2, A->iso ? nullptr : (T *)vx2);
+            hipLaunchKernelGGL(k_resize_fill<T>, dim3(gb_grid(keep, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0,
+                               gb_stream(), A->rowptr, A->colidx, (const T *)A->vals, keep, ncols, rp2, ci2,
+                               A->iso ? nullptr : (T *)vx2);
         });
         GB_LAUNCH_CHECK();
     }
@@ -1061,7 +1030,7 @@ static void matrix_resize(GB_Obj *A, int64_t nrows, int64_t ncols) {
 }
 
 __global__ void k_bits_truncate(uint64_t *__restrict__ bits, int64_t nw_new, int64_t n_new) {
-    GRID_STRIDE(w, nw_new) {
+    GB_GRID_LOOP(w, nw_new) {
         int64_t lo = w << 6;
         if (lo + 64 > n_new) {
             int keep = (int)(n_new - lo);
@@ -1076,7 +1045,8 @@ static void vector_resize(GB_Obj *v, int64_t n) {
     gb_memset(bits, 0, nw * sizeof(uint64_t));
     gb_copy_d2d(bits, v->bits, std::min(nw, nw_old) * sizeof(uint64_t));
     if (n < v->nrows && nw) {
-        hipLaunchKernelGGL(k_bits_truncate, dim3(grid_for(nw)), dim3(GB_BLOCK), 0, gb_stream(), bits, nw, n);
+        hipLaunchKernelGGL(k_bits_truncate, dim3(gb_grid(nw, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0, gb_stream(),
+                           bits, nw, n);
         GB_LAUNCH_CHECK();
     }
     void *dense = nullptr;
@@ -1310,7 +1280,7 @@ GrB_Info GrB_Scalar_error(const char **error, const GrB_Scalar s) {
     GrB_Info GrB_Matrix_setElement_##T(GrB_Matrix C, ctype x, GrB_Index i, GrB_Index j) {                    \
         return gb_api(OBJ(C), [&] {                                                                          \
             GB_Obj *o = gb_obj_check(C);                                                                     \
-            with_type(o->type->code, [&](auto z) {                                                           \
+            gb_with_type(o->type->code, [&](auto z) {                                                           \
                 using S = decltype(z);                                                                       \
                 if (o->kind == GB_KIND_MATRIX) matrix_set_element<S>(o, gb_cast<S, ctype>(x), i, j);         \
                 else {                                                                                       \
@@ -1540,7 +1510,7 @@ GrB_Info GxB_Vector_bitmap_import(GrB_Vector v, const void *src, GrB_Index nword
         // every imported entry carries the value 1 (true): an iso vector
         size_t ts = o->type->size;
         char one[16] = {0};
-        with_type(o->type->code, [&](auto z) {
+        gb_with_type(o->type->code, [&](auto z) {
             using T = decltype(z);
             T x = (T)1;
             memcpy(one, &x, sizeof(T));

@@ -14,14 +14,7 @@
 #include "gb_internal.h"
 
 #define OPS_BLOCK 256
-static inline unsigned ops_grid(int64_t n, unsigned cap = 16384) {
-    int64_t g = (n + OPS_BLOCK - 1) / OPS_BLOCK;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
-}
-#define OPS_STRIDE(i, n) \
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
+#define OPS_GRID_CAP 16384  // blocks, unless the launch names its own cap
 
 // ================================================================== mxm
 static void do_mxm(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_Semiring sr, GB_Obj *A, GB_Obj *B,
@@ -88,7 +81,7 @@ __global__ void k_ewise_mat(int64_t nrows, int op, bool add, const int64_t *__re
                             const int32_t *__restrict__ aci, const X *__restrict__ ax, bool a_iso,
                             const int64_t *__restrict__ brp, const int32_t *__restrict__ bci, const X *__restrict__ bx,
                             bool b_iso, int64_t *__restrict__ orp, int32_t *__restrict__ oci, Z *__restrict__ oz) {
-    OPS_STRIDE(i, nrows) {
+    GB_GRID_LOOP(i, nrows) {
         int64_t pa = arp[i], ea = arp[i + 1], pb = brp[i], eb = brp[i + 1];
         int64_t o = FILL ? orp[i] : 0;
         while (pa < ea || pb < eb) {
@@ -112,23 +105,6 @@ __global__ void k_ewise_mat(int64_t nrows, int op, bool add, const int64_t *__re
     }
 }
 
-template <class F>
-static void dispatch_xz(int xcode, int zcode, F &&f) {
-    if (xcode == zcode) {
-        gb_with_type(xcode, [&](auto x) {
-            using X = decltype(x);
-            f(X{}, X{});
-        });
-    } else if (zcode == GBAMD_T_BOOL) {
-        gb_with_type(xcode, [&](auto x) {
-            using X = decltype(x);
-            f(X{}, bool{});
-        });
-    } else {
-        gb_throw(GrB_NOT_IMPLEMENTED, "operator type combination not supported");
-    }
-}
-
 static void do_ewise(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_BinaryOp op, GB_Obj *A, GB_Obj *B,
                      const gb_desc &d, bool add) {
     gb_check_binop(op, false);
@@ -145,20 +121,16 @@ static void do_ewise(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_BinaryOp op, 
         gb_get_bitmap(ub, B);
         gb_scratch s;
         const void *xa = gb_bitmap_vals_as(ua, xcode, s), *xb = gb_bitmap_vals_as(ub, xcode, s);
-        gb_vec_result T;
-        T.n = n;
-        T.tcode = zcode;
-        T.bits = gb_malloc_n<uint64_t>(gb_words(n));
-        T.dense = gb_malloc(n * gb_type_size(zcode));
-        T.d_nvals = gb_malloc_n<int64_t>(1);
+        gb_vec_result T = gb_new_vec_result(n, zcode, false);
         gb_memset(T.d_nvals, 0, sizeof(int64_t));
-        dispatch_xz(xcode, zcode, [&](auto x, auto z) {
+        gb_dispatch_xz(xcode, zcode, [&](auto x, auto z) {
             using X = decltype(x);
             using Z = decltype(z);
             if (n)
-                hipLaunchKernelGGL((k_ewise_vec<X, Z>), dim3(ops_grid(n, 1024)), dim3(OPS_BLOCK), 0, gb_stream(), n,
-                                   op->opcode, add, ua.bits, (const X *)xa, ua.iso, ub.bits, (const X *)xb, ub.iso,
-                                   T.bits, (Z *)T.dense, (unsigned long long *)T.d_nvals, gb_device_state());
+                hipLaunchKernelGGL((k_ewise_vec<X, Z>), dim3(gb_grid(n, OPS_BLOCK, 1024)), dim3(OPS_BLOCK), 0,
+                                   gb_stream(), n, op->opcode, add, ua.bits, (const X *)xa, ua.iso, ub.bits,
+                                   (const X *)xb, ub.iso, T.bits, (Z *)T.dense, (unsigned long long *)T.d_nvals,
+                                   gb_device_state());
         });
         GB_LAUNCH_CHECK();
         gb_writeback_vector(C, T, M, d, accum, false);
@@ -181,22 +153,22 @@ static void do_ewise(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_BinaryOp op, 
     T.tcode = zcode;
     int64_t *cnt = s.get<int64_t>(nr + 1);
     T.rowptr = gb_malloc_n<int64_t>(nr + 1);
-    dispatch_xz(xcode, zcode, [&](auto x, auto z) {
+    gb_dispatch_xz(xcode, zcode, [&](auto x, auto z) {
         using X = decltype(x);
         using Z = decltype(z);
         if (nr)
-            hipLaunchKernelGGL((k_ewise_mat<X, Z, false>), dim3(ops_grid(nr)), dim3(OPS_BLOCK), 0, gb_stream(), nr,
-                               op->opcode, add, av.rowptr, av.colidx, (const X *)xa, av.iso, bv.rowptr, bv.colidx,
-                               (const X *)xb, bv.iso, cnt, nullptr, nullptr);
+            hipLaunchKernelGGL((k_ewise_mat<X, Z, false>), dim3(gb_grid(nr, OPS_BLOCK, OPS_GRID_CAP)), dim3(OPS_BLOCK),
+                               0, gb_stream(), nr, op->opcode, add, av.rowptr, av.colidx, (const X *)xa, av.iso,
+                               bv.rowptr, bv.colidx, (const X *)xb, bv.iso, cnt, nullptr, nullptr);
         GB_LAUNCH_CHECK();
         gb_exclusive_scan_i64(cnt, T.rowptr, nr);
         T.nvals = gb_read_i64(T.rowptr + nr);
         T.colidx = gb_malloc_n<int32_t>(T.nvals);
         T.vals = gb_malloc(T.nvals * sizeof(Z));
         if (nr)
-            hipLaunchKernelGGL((k_ewise_mat<X, Z, true>), dim3(ops_grid(nr)), dim3(OPS_BLOCK), 0, gb_stream(), nr,
-                               op->opcode, add, av.rowptr, av.colidx, (const X *)xa, av.iso, bv.rowptr, bv.colidx,
-                               (const X *)xb, bv.iso, T.rowptr, T.colidx, (Z *)T.vals);
+            hipLaunchKernelGGL((k_ewise_mat<X, Z, true>), dim3(gb_grid(nr, OPS_BLOCK, OPS_GRID_CAP)), dim3(OPS_BLOCK),
+                               0, gb_stream(), nr, op->opcode, add, av.rowptr, av.colidx, (const X *)xa, av.iso,
+                               bv.rowptr, bv.colidx, (const X *)xb, bv.iso, T.rowptr, T.colidx, (Z *)T.vals);
         GB_LAUNCH_CHECK();
     });
     gb_writeback_matrix(C, T, M, d, accum);
@@ -213,7 +185,7 @@ __global__ void k_reduce_partial(int mon, const T *__restrict__ vals, bool iso, 
     T acc = T();
     bool found = false;
     int64_t total = bits ? n : nvals;
-    OPS_STRIDE(i, total) {
+    GB_GRID_LOOP(i, total) {
         if (bits && !gb_bit(bits, i)) continue;
         T v = vals[iso ? 0 : i];
         acc = found ? gb_monoid<T>(mon, acc, v) : v;
@@ -309,19 +281,10 @@ static void monoid_identity(GrB_Monoid monoid, void *out) {
 // ================================================================== transpose
 // T = a copy of a CSR view (transpose, matrix assign)
 static void copy_csr_T(gb_mat_result &T, const gb_csr_view &v) {
-    T.nrows = v.nrows;
-    T.ncols = v.ncols;
-    T.nvals = v.nvals;
-    T.tcode = v.tcode;
-    T.iso = v.iso;
-    const size_t ts = gb_type_size(v.tcode);
-    T.rowptr = gb_malloc_n<int64_t>(v.nrows + 1);
+    T = gb_new_mat_result(v.nrows, v.ncols, v.tcode, v.nvals, v.iso);
     gb_copy_d2d(T.rowptr, v.rowptr, (v.nrows + 1) * sizeof(int64_t));
-    T.colidx = gb_malloc_n<int32_t>(v.nvals);
     gb_copy_d2d(T.colidx, v.colidx, v.nvals * sizeof(int32_t));
-    const int64_t nv = v.iso ? 1 : v.nvals;
-    T.vals = gb_malloc(nv * ts);
-    gb_copy_d2d(T.vals, v.vals, nv * ts);
+    gb_copy_d2d(T.vals, v.vals, (v.iso ? 1 : v.nvals) * gb_type_size(v.tcode));
 }
 // the values, bitmap and count of T (n positions) = a copy of a bitmap view (vector assign)
 static void copy_bitmap_T(gb_vec_result &T, const gb_bitmap_view &v, int64_t n) {
@@ -348,14 +311,9 @@ static void do_transpose(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GB_Obj *A, co
 // ================================================================== assign
 // T for "x assigned at every index of I (GrB_ALL: all)": iso bitmap vector
 static void scalar_vec_T(gb_vec_result &T, int64_t n, const GrB_Index *I, int64_t ni, const void *x, int code) {
-    T.n = n;
-    T.tcode = code;
-    T.iso = true;
+    T = gb_new_vec_result(n, code, true);
     int64_t nw = gb_words(n);
-    T.bits = gb_malloc_n<uint64_t>(nw);
-    T.dense = gb_malloc(gb_type_size(code));
     gb_copy_h2d(T.dense, x, gb_type_size(code));
-    T.d_nvals = gb_malloc_n<int64_t>(1);
     if (I == GrB_ALL) {
         std::vector<uint64_t> hb(nw, ~0ULL);
         if (n & 63) hb[nw - 1] = (1ULL << (n & 63)) - 1;
@@ -572,15 +530,7 @@ static void matrix_assign_scalar(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, const
     std::vector<int32_t> ci(nz);
     for (size_t a = 0; a < rows.size(); a++)
         for (size_t b = 0; b < cols.size(); b++) ci[a * cols.size() + b] = (int32_t)cols[b];
-    gb_mat_result T;
-    T.nrows = nr;
-    T.ncols = nc;
-    T.nvals = nz;
-    T.tcode = ct;
-    T.iso = true;
-    T.rowptr = gb_malloc_n<int64_t>(nr + 1);
-    T.colidx = gb_malloc_n<int32_t>(nz);
-    T.vals = gb_malloc(gb_type_size(ct));
+    gb_mat_result T = gb_new_mat_result(nr, nc, ct, nz, true);
     gb_copy_h2d(T.rowptr, rp.data(), (nr + 1) * sizeof(int64_t));
     gb_copy_h2d(T.colidx, ci.data(), nz * sizeof(int32_t));
     gb_copy_h2d(T.vals, xc, gb_type_size(ct));
@@ -596,7 +546,7 @@ static void matrix_assign_scalar(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, const
 // over the n stored values (n = 1 for iso inputs): structure is not touched.
 template <class X, class Z>
 __global__ void k_apply(int64_t n, int kind, int op, const X *__restrict__ in, X s, Z *__restrict__ out) {
-    OPS_STRIDE(i, n) {
+    GB_GRID_LOOP(i, n) {
         X x = in[i];
         if (kind == 0) out[i] = gb_cast<Z, X>(gb_unop<X>(op, x));
         else if (kind == 1) out[i] = gb_binop_z<X, Z>(op, s, x, 0, 0, 0);
@@ -626,14 +576,14 @@ static void do_apply(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, int kind, GrB_Una
     char sx[16] = {0};
     if (kind != 0) gb_cast_scalar(sx, xcode, sval, scode);
     auto launch = [&](int64_t n, const void *in, void *out) {
-        dispatch_xz(xcode, zcode, [&](auto x, auto z) {
+        gb_dispatch_xz(xcode, zcode, [&](auto x, auto z) {
             using X = decltype(x);
             using Z = decltype(z);
             X s;
             memcpy(&s, sx, sizeof(X));
             if (n)
-                hipLaunchKernelGGL((k_apply<X, Z>), dim3(ops_grid(n)), dim3(OPS_BLOCK), 0, gb_stream(), n, kind,
-                                   opcode, (const X *)in, s, (Z *)out);
+                hipLaunchKernelGGL((k_apply<X, Z>), dim3(gb_grid(n, OPS_BLOCK, OPS_GRID_CAP)), dim3(OPS_BLOCK), 0,
+                                   gb_stream(), n, kind, opcode, (const X *)in, s, (Z *)out);
         });
         GB_LAUNCH_CHECK();
     };
@@ -644,17 +594,10 @@ static void do_apply(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, int kind, GrB_Una
         gb_get_bitmap(uv, A);
         gb_scratch s;
         const void *xin = gb_bitmap_vals_as(uv, xcode, s);
-        gb_vec_result T;
-        T.n = uv.n;
-        T.tcode = zcode;
-        T.iso = uv.iso;
+        gb_vec_result T = gb_new_vec_result(uv.n, zcode, uv.iso);
         const int64_t nw = gb_words(uv.n);
-        T.bits = gb_malloc_n<uint64_t>(std::max<int64_t>(nw, 1));
         if (nw) gb_copy_d2d(T.bits, uv.bits, nw * sizeof(uint64_t));
-        const int64_t nv = uv.iso ? 1 : uv.n;
-        T.dense = gb_malloc(std::max<int64_t>(nv, 1) * zs);
-        launch(nv, xin, T.dense);
-        T.d_nvals = gb_malloc_n<int64_t>(1);
+        launch(uv.iso ? 1 : uv.n, xin, T.dense);
         if (uv.count) gb_copy_d2d(T.d_nvals, uv.count, sizeof(int64_t));
         else gb_bitmap_count(T.bits, T.n, T.d_nvals);
         gb_writeback_vector(C, T, M, d, accum, false);
@@ -666,19 +609,10 @@ static void do_apply(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, int kind, GrB_Una
     GB_REQUIRE(v.nrows == C->nrows && v.ncols == C->ncols, GrB_DIMENSION_MISMATCH, "matrix dimensions do not match");
     gb_scratch s;
     const void *xin = gb_view_vals_as(v, xcode, s);
-    gb_mat_result T;
-    T.nrows = v.nrows;
-    T.ncols = v.ncols;
-    T.nvals = v.nvals;
-    T.tcode = zcode;
-    T.iso = v.iso;
-    T.rowptr = gb_malloc_n<int64_t>(v.nrows + 1);
+    gb_mat_result T = gb_new_mat_result(v.nrows, v.ncols, zcode, v.nvals, v.iso);
     gb_copy_d2d(T.rowptr, v.rowptr, (v.nrows + 1) * sizeof(int64_t));
-    T.colidx = gb_malloc_n<int32_t>(std::max<int64_t>(v.nvals, 1));
     if (v.nvals) gb_copy_d2d(T.colidx, v.colidx, v.nvals * sizeof(int32_t));
-    const int64_t nv = v.iso ? (v.nvals ? 1 : 0) : v.nvals;
-    T.vals = gb_malloc(std::max<int64_t>(nv, 1) * zs);
-    launch(nv, xin, T.vals);
+    launch(v.iso ? (v.nvals ? 1 : 0) : v.nvals, xin, T.vals);
     gb_writeback_matrix(C, T, M, d, accum);
 }
 
@@ -801,7 +735,7 @@ GrB_Info GrB_transpose(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp a
 // that u does not hold are deleted.  Clears those bits before the merge with accum SECOND.
 __global__ void k_clear_region(int64_t nw, uint64_t *__restrict__ wbits, const uint64_t *__restrict__ rbits,
                                const uint64_t *__restrict__ mbits, bool mcomp) {
-    OPS_STRIDE(k, nw) {
+    GB_GRID_LOOP(k, nw) {
         uint64_t sel = mbits ? (mcomp ? ~mbits[k] : mbits[k]) : ~0ULL;
         wbits[k] &= ~(rbits[k] & sel);
     }
@@ -818,8 +752,8 @@ static void vector_clear_region(GB_Obj *W, const gb_index_list &L, GB_Obj *M, co
     gb_copy_h2d(r, hr.data(), nw * sizeof(uint64_t));
     gb_vmask m;
     gb_make_vmask(m, M, d, n);
-    hipLaunchKernelGGL(k_clear_region, dim3(ops_grid(nw)), dim3(OPS_BLOCK), 0, gb_stream(), nw, W->bits, r, m.bits,
-                       m.comp);
+    hipLaunchKernelGGL(k_clear_region, dim3(gb_grid(nw, OPS_BLOCK, OPS_GRID_CAP)), dim3(OPS_BLOCK), 0, gb_stream(), nw,
+                       W->bits, r, m.bits, m.comp);
     GB_LAUNCH_CHECK();
     gb_vec_recount(W);
     gb_sync();
@@ -912,16 +846,10 @@ GrB_Info GrB_Matrix_reduce_Monoid_Scalar(GrB_Scalar s, const GrB_BinaryOp accum,
         GB_Obj *S = gb_obj_check(s);
         char v[16];
         bool any = reduce_values(gb_obj_check(A), monoid, v);
-        gb_vec_result T;
-        T.n = 1;
-        T.tcode = monoid->type->code;
-        T.iso = true;
-        T.bits = gb_malloc_n<uint64_t>(1);
+        gb_vec_result T = gb_new_vec_result(1, monoid->type->code, true);
         uint64_t b = any ? 1 : 0;
         gb_copy_h2d(T.bits, &b, sizeof(b));
-        T.dense = gb_malloc(16);
         gb_copy_h2d(T.dense, v, gb_type_size(T.tcode));
-        T.d_nvals = gb_malloc_n<int64_t>(1);
         int64_t nn = any ? 1 : 0;
         gb_copy_h2d(T.d_nvals, &nn, sizeof(nn));
         gb_sync();

@@ -11,18 +11,13 @@
 
 #define GB_BLOCK 256
 
-static inline unsigned gb_grid(int64_t n, int per_block = GB_BLOCK) {
-    int64_t g = (n + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    if (g > (1LL << 30)) g = 1LL << 30;
-    return (unsigned)g;
-}
+#define PRIM_GRID_CAP (1LL << 30)  // for the launches that set no cap of their own
 
 // ------------------------------------------------------------------ scans / sorts
 // out[0..len) += *carry (the previous chunk's last prefix, already final on the stream)
 __global__ void k_add_carry(int64_t *__restrict__ out, int64_t len, const int64_t *__restrict__ carry) {
     const int64_t c = *carry;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < len; i += (int64_t)gridDim.x * blockDim.x)
+    GB_GRID_LOOP(i, len)
         out[i] += c;
 }
 
@@ -45,8 +40,8 @@ static void scan_chunked(It in, int64_t *out, int64_t n) {
         size_t tb = tmp;
         GB_HIP(hipcub::DeviceScan::InclusiveSum(t, tb, in + off, out + 1 + off, (int)len, gb_stream()));
         if (off) {
-            hipLaunchKernelGGL(k_add_carry, dim3(gb_grid(len, GB_BLOCK * 8)), dim3(GB_BLOCK), 0, gb_stream(),
-                               out + 1 + off, len, out + off);
+            hipLaunchKernelGGL(k_add_carry, dim3(gb_grid(len, GB_BLOCK * 8, PRIM_GRID_CAP)), dim3(GB_BLOCK), 0,
+                               gb_stream(), out + 1 + off, len, out + off);
             GB_LAUNCH_CHECK();
         }
     }
@@ -279,8 +274,7 @@ void gb_exclusive_scan_u8(const uint8_t *in, int64_t *out, int64_t n) {
 }
 
 __global__ void k_iota(int64_t *x, int64_t n) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x)
+    GB_GRID_LOOP(i, n)
         x[i] = i;
 }
 
@@ -325,15 +319,13 @@ void gb_sort_pairs_i32(int32_t *keys, int64_t *vals, int64_t n, int end_bit) {
 // ------------------------------------------------------------------ casts
 template <class D, class S>
 __global__ void k_cast(D *__restrict__ dst, const S *__restrict__ src, int64_t n) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x)
+    GB_GRID_LOOP(i, n)
         dst[i] = gb_cast<D, S>(src[i]);
 }
 
 template <class D>
 static void cast_from(void *dst, const void *src, int src_code, int64_t n) {
-    unsigned g = gb_grid(n);
-    if (g > 4096) g = 4096;
+    unsigned g = gb_grid(n, GB_BLOCK, 4096);
 #define GB_CASE(code, S)                                                                        \
     case code:                                                                                  \
         hipLaunchKernelGGL((k_cast<D, S>), dim3(g), dim3(GB_BLOCK), 0, gb_stream(), (D *)dst, \
@@ -381,22 +373,18 @@ void gb_cast_array(void *dst, int dst_code, const void *src, int src_code, int64
 template <class W>
 __global__ void k_fill(W *__restrict__ dst, const W *__restrict__ one, int64_t n) {
     W v = *one;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x)
+    GB_GRID_LOOP(i, n)
         dst[i] = v;
 }
 
 void *gb_expand_iso(const void *one_value, size_t tsize, int64_t n) {
     void *out = gb_malloc(n * tsize);
     if (n == 0) return out;
-    unsigned g = gb_grid(n);
-    if (g > 4096) g = 4096;
-    switch (tsize) {
-    case 1: hipLaunchKernelGGL(k_fill<uint8_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), (uint8_t *)out, (const uint8_t *)one_value, n); break;
-    case 2: hipLaunchKernelGGL(k_fill<uint16_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), (uint16_t *)out, (const uint16_t *)one_value, n); break;
-    case 4: hipLaunchKernelGGL(k_fill<uint32_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), (uint32_t *)out, (const uint32_t *)one_value, n); break;
-    default: hipLaunchKernelGGL(k_fill<uint64_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), (uint64_t *)out, (const uint64_t *)one_value, n); break;
-    }
+    unsigned g = gb_grid(n, GB_BLOCK, 4096);
+    gb_with_size(tsize, [&](auto w) {
+        using W = decltype(w);
+        hipLaunchKernelGGL(k_fill<W>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), (W *)out, (const W *)one_value, n);
+    });
     GB_LAUNCH_CHECK();
     return out;
 }
@@ -409,8 +397,7 @@ __global__ void k_bitmap_count(const uint64_t *__restrict__ bits, int64_t nwords
     if (threadIdx.x == 0) part = 0;
     __syncthreads();
     unsigned long long c = 0;
-    for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w < nwords;
-         w += (int64_t)gridDim.x * blockDim.x)
+    GB_GRID_LOOP(w, nwords)
         c += __popcll(bits[w]);
     for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
     if ((threadIdx.x & 63) == 0) atomicAdd(&part, c);
@@ -423,8 +410,7 @@ __global__ void k_bitmap_count(const uint64_t *__restrict__ bits, int64_t nwords
 __global__ void k_bitmap_count_store(const uint64_t *__restrict__ bits, int64_t nwords, int64_t *__restrict__ count,
                                      unsigned long long *__restrict__ gst, gb_host_slot *pub, long long seq) {
     long long c = 0;
-    for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w < nwords;
-         w += (int64_t)gridDim.x * blockDim.x)
+    GB_GRID_LOOP(w, nwords)
         c += __popcll(bits[w]);
     long long tot;
     if (gb_grid_sum(c, gst, &tot)) {
@@ -439,8 +425,7 @@ __global__ void k_bitmap_count_store(const uint64_t *__restrict__ bits, int64_t 
 
 void gb_bitmap_count_pub(const uint64_t *bits, int64_t n, int64_t *d_count, gb_host_slot *pub_host, uint64_t seq) {
     const int64_t nw = gb_words(n);
-    unsigned g = gb_grid(nw);
-    if (g > 512) g = 512;
+    unsigned g = gb_grid(nw, GB_BLOCK, 512);
     hipLaunchKernelGGL(k_bitmap_count_store, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), bits, nw, d_count,
                        gb_device_state(), pub_host ? gb_host_slot_device(pub_host) : nullptr, (long long)seq);
     GB_LAUNCH_CHECK();
@@ -453,8 +438,7 @@ __global__ void k_zero_bitmap(uint64_t *__restrict__ bits, int64_t nw, int64_t *
 }
 
 void gb_zero_bitmap(uint64_t *bits, int64_t nw, int64_t *d_count) {
-    unsigned g = gb_grid(nw);
-    if (g > 1024) g = 1024;
+    unsigned g = gb_grid(nw, GB_BLOCK, 1024);
     hipLaunchKernelGGL(k_zero_bitmap, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), bits, nw, d_count);
     GB_LAUNCH_CHECK();
 }
@@ -465,8 +449,7 @@ void gb_bitmap_count(const uint64_t *bits, int64_t n, int64_t *d_count) {
 
 // per-word popcount -> exclusive scan -> positions
 __global__ void k_word_pop(const uint64_t *__restrict__ bits, int64_t nwords, int64_t *__restrict__ pop) {
-    for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w < nwords;
-         w += (int64_t)gridDim.x * blockDim.x)
+    GB_GRID_LOOP(w, nwords)
         pop[w] = __popcll(bits[w]);
 }
 
@@ -476,8 +459,7 @@ __global__ void k_bitmap_scatter(const uint64_t *__restrict__ bits, const W *__r
                                  int64_t *__restrict__ rowptr_n1, int32_t *__restrict__ colidx,
                                  W *__restrict__ vals) {
     // n x 1 CSR: row i has one entry (col 0) iff bit i set.  rowptr[i] = rank(i).
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
+    GB_GRID_LOOP(i, n) {
         uint64_t w = bits[i >> 6];
         int b = i & 63;
         int64_t rank = woff[i >> 6] + __popcll(w & ((b == 0) ? 0ULL : (~0ULL >> (64 - b))));
@@ -495,7 +477,7 @@ void gb_bitmap_to_csr(const uint64_t *bits, const void *dense, bool iso, int64_t
     int64_t *pop = gb_malloc_n<int64_t>(nw + 1);
     int64_t *woff = gb_malloc_n<int64_t>(nw + 1);
     if (nw) {
-        unsigned g = gb_grid(nw);
+        unsigned g = gb_grid(nw, GB_BLOCK, PRIM_GRID_CAP);
         hipLaunchKernelGGL(k_word_pop, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), bits, nw, pop);
         GB_LAUNCH_CHECK();
     }
@@ -506,15 +488,13 @@ void gb_bitmap_to_csr(const uint64_t *bits, const void *dense, bool iso, int64_t
     void *vx = iso ? gb_malloc(tsize) : gb_malloc(nz * tsize);
     if (iso) gb_copy_d2d(vx, dense, tsize);
     if (n) {
-        unsigned g = gb_grid(n);
-        if (g > 8192) g = 8192;
+        unsigned g = gb_grid(n, GB_BLOCK, 8192);
         void *vout = iso ? nullptr : vx;
-        switch (tsize) {
-        case 1: hipLaunchKernelGGL(k_bitmap_scatter<uint8_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), bits, (const uint8_t *)dense, false, n, woff, rp, ci, (uint8_t *)vout); break;
-        case 2: hipLaunchKernelGGL(k_bitmap_scatter<uint16_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), bits, (const uint16_t *)dense, false, n, woff, rp, ci, (uint16_t *)vout); break;
-        case 4: hipLaunchKernelGGL(k_bitmap_scatter<uint32_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), bits, (const uint32_t *)dense, false, n, woff, rp, ci, (uint32_t *)vout); break;
-        default: hipLaunchKernelGGL(k_bitmap_scatter<uint64_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), bits, (const uint64_t *)dense, false, n, woff, rp, ci, (uint64_t *)vout); break;
-        }
+        gb_with_size(tsize, [&](auto w) {
+            using W = decltype(w);
+            hipLaunchKernelGGL(k_bitmap_scatter<W>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), bits, (const W *)dense,
+                               false, n, woff, rp, ci, (W *)vout);
+        });
         GB_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(k_copy_i64, dim3(1), dim3(1), 0, gb_stream(), rp + n, woff + nw);
@@ -556,14 +536,13 @@ void gb_csr_col_to_bitmap(const gb_csr_view &v, size_t tsize, uint64_t **bits, v
     void *d = v.iso ? gb_malloc(tsize) : gb_malloc(n * tsize);
     if (v.iso) gb_copy_d2d(d, v.vals, tsize);
     if (nw) {
-        unsigned g = gb_grid(nw);
+        unsigned g = gb_grid(nw, GB_BLOCK, PRIM_GRID_CAP);
         void *dout = v.iso ? nullptr : d;
-        switch (tsize) {
-        case 1: hipLaunchKernelGGL(k_csr_col_to_bitmap<uint8_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), v.rowptr, (const uint8_t *)v.vals, false, n, b, (uint8_t *)dout); break;
-        case 2: hipLaunchKernelGGL(k_csr_col_to_bitmap<uint16_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), v.rowptr, (const uint16_t *)v.vals, false, n, b, (uint16_t *)dout); break;
-        case 4: hipLaunchKernelGGL(k_csr_col_to_bitmap<uint32_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), v.rowptr, (const uint32_t *)v.vals, false, n, b, (uint32_t *)dout); break;
-        default: hipLaunchKernelGGL(k_csr_col_to_bitmap<uint64_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), v.rowptr, (const uint64_t *)v.vals, false, n, b, (uint64_t *)dout); break;
-        }
+        gb_with_size(tsize, [&](auto w) {
+            using W = decltype(w);
+            hipLaunchKernelGGL(k_csr_col_to_bitmap<W>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), v.rowptr,
+                               (const W *)v.vals, false, n, b, (W *)dout);
+        });
         GB_LAUNCH_CHECK();
     }
     int64_t *cnt = gb_malloc_n<int64_t>(1);
@@ -574,20 +553,25 @@ void gb_csr_col_to_bitmap(const gb_csr_view &v, size_t tsize, uint64_t **bits, v
 }
 
 // ------------------------------------------------------------------ transpose
-__global__ void k_expand_rows(const int64_t *__restrict__ rowptr, int64_t nrows,
-                              int64_t *__restrict__ rowof) {
-    // one wave per row
+// one wave per row of [r0, r1): rowof[e - pbase] = the row of entry e
+__global__ void k_rowof(const int64_t *__restrict__ rowptr, int64_t r0, int64_t r1, int64_t pbase,
+                        int64_t *__restrict__ rowof) {
     int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
     int lane = threadIdx.x & 63;
     int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t i = wave; i < nrows; i += nw)
-        for (int64_t p = rowptr[i] + lane; p < rowptr[i + 1]; p += 64) rowof[p] = i;
+    for (int64_t i = r0 + wave; i < r1; i += nw)
+        for (int64_t p = rowptr[i] + lane; p < rowptr[i + 1]; p += 64) rowof[p - pbase] = i;
+}
+
+void gb_rows_of(const int64_t *rowptr, int64_t r0, int64_t r1, int64_t pbase, int64_t *out, int64_t grid_cap) {
+    hipLaunchKernelGGL(k_rowof, dim3(gb_grid(r1 - r0, GB_BLOCK / 64, grid_cap)), dim3(GB_BLOCK), 0, gb_stream(), rowptr,
+                       r0, r1, pbase, out);
+    GB_LAUNCH_CHECK();
 }
 
 __global__ void k_count_cols(const int32_t *__restrict__ colidx, int64_t nvals,
                              unsigned long long *__restrict__ cnt) {
-    for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < nvals;
-         p += (int64_t)gridDim.x * blockDim.x)
+    GB_GRID_LOOP(p, nvals)
         atomicAdd(&cnt[colidx[p]], 1ULL);
 }
 
@@ -595,8 +579,7 @@ template <class W>
 __global__ void k_transpose_fill(const int64_t *__restrict__ perm, const int64_t *__restrict__ rowof,
                                  const W *__restrict__ vals, int64_t nvals,
                                  int32_t *__restrict__ tcol, W *__restrict__ tvals) {
-    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < nvals;
-         q += (int64_t)gridDim.x * blockDim.x) {
+    GB_GRID_LOOP(q, nvals) {
         int64_t p = perm[q];
         tcol[q] = (int32_t)rowof[p];
         if (tvals) tvals[q] = vals[p];
@@ -614,8 +597,7 @@ void gb_transpose_csr(int64_t nrows, int64_t ncols, int64_t nvals, const int64_t
     int64_t *cnt = gb_malloc_n<int64_t>(ncols + 1);
     gb_memset(cnt, 0, (ncols + 1) * sizeof(int64_t));
     if (nvals) {
-        unsigned g = gb_grid(nvals);
-        if (g > 8192) g = 8192;
+        unsigned g = gb_grid(nvals, GB_BLOCK, 8192);
         hipLaunchKernelGGL(k_count_cols, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), colidx, nvals,
                            (unsigned long long *)cnt);
         GB_LAUNCH_CHECK();
@@ -628,29 +610,24 @@ void gb_transpose_csr(int64_t nrows, int64_t ncols, int64_t nvals, const int64_t
         int64_t *perm = gb_malloc_n<int64_t>(nvals);
         int64_t *rowof = gb_malloc_n<int64_t>(nvals);
         gb_copy_d2d(keys, colidx, nvals * sizeof(int32_t));
-        hipLaunchKernelGGL(k_expand_rows, dim3(gb_grid(nrows * 64 > (1LL << 24) ? (1LL << 24) : nrows * 64)),
-                           dim3(GB_BLOCK), 0, gb_stream(), rowptr, nrows, rowof);
-        GB_LAUNCH_CHECK();
+        gb_rows_of(rowptr, 0, nrows, 0, rowof, 1 << 16);
         // perm = 0..nvals-1 : reuse rowof-type iota via thrust-free kernel
         int64_t *iota = perm;
         {
-            unsigned g = gb_grid(nvals);
-            if (g > 8192) g = 8192;
+            unsigned g = gb_grid(nvals, GB_BLOCK, 8192);
             hipLaunchKernelGGL(k_iota, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), iota, nvals);
             GB_LAUNCH_CHECK();
         }
         int bits = 1;
         while (bits < 31 && (1LL << bits) < ncols) bits++;
         gb_sort_pairs_i32(keys, perm, nvals, bits);
-        unsigned g = gb_grid(nvals);
-        if (g > 8192) g = 8192;
+        unsigned g = gb_grid(nvals, GB_BLOCK, 8192);
         void *vout = (vals && !iso) ? tvx : nullptr;
-        switch (tsize) {
-        case 1: hipLaunchKernelGGL(k_transpose_fill<uint8_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), perm, rowof, (const uint8_t *)vals, nvals, tci, (uint8_t *)vout); break;
-        case 2: hipLaunchKernelGGL(k_transpose_fill<uint16_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), perm, rowof, (const uint16_t *)vals, nvals, tci, (uint16_t *)vout); break;
-        case 4: hipLaunchKernelGGL(k_transpose_fill<uint32_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), perm, rowof, (const uint32_t *)vals, nvals, tci, (uint32_t *)vout); break;
-        default: hipLaunchKernelGGL(k_transpose_fill<uint64_t>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), perm, rowof, (const uint64_t *)vals, nvals, tci, (uint64_t *)vout); break;
-        }
+        gb_with_size(tsize, [&](auto w) {
+            using W = decltype(w);
+            hipLaunchKernelGGL(k_transpose_fill<W>, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), perm, rowof,
+                               (const W *)vals, nvals, tci, (W *)vout);
+        });
         GB_LAUNCH_CHECK();
         gb_free(keys);
         if (tperm) {
@@ -676,24 +653,23 @@ void gb_transpose_csr(int64_t nrows, int64_t ncols, int64_t nvals, const int64_t
 // carry INT32_MIN | rank instead of the column, the rest keep their column.  Built once per
 // matrix version and orientation (freed with the other cached views).
 __global__ void k_hot_count(const int32_t *__restrict__ colidx, int64_t nvals, uint32_t *__restrict__ cnt) {
-    for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < nvals; p += (int64_t)gridDim.x * blockDim.x)
+    GB_GRID_LOOP(p, nvals)
         atomicAdd(&cnt[colidx[p]], 1u);
 }
 
 __global__ void k_iota_i32(int32_t *__restrict__ out, int64_t n) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    GB_GRID_LOOP(i, n)
         out[i] = (int32_t)i;
 }
 
 __global__ void k_hot_rank(const int32_t *__restrict__ hot, int64_t nh, int32_t *__restrict__ rank) {
-    for (int64_t h = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; h < nh; h += (int64_t)gridDim.x * blockDim.x)
+    GB_GRID_LOOP(h, nh)
         rank[hot[h]] = (int32_t)h;
 }
 
 __global__ void k_hot_remap(const int32_t *__restrict__ colidx, int64_t nvals, const int32_t *__restrict__ rank,
                             int32_t *__restrict__ out) {
-    for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < nvals;
-         p += (int64_t)gridDim.x * blockDim.x) {
+    GB_GRID_LOOP(p, nvals) {
         const int32_t c = colidx[p], r = rank[c];
         out[p] = r >= 0 ? (int32_t)((uint32_t)r | 0x80000000u) : c;
     }
@@ -715,12 +691,10 @@ void gb_view_hot(gb_csr_view &v, GB_Obj *A, int orient) {
         uint32_t *cnt = s.get<uint32_t>(nc), *cnt2 = s.get<uint32_t>(nc);
         int32_t *ids = s.get<int32_t>(nc), *ids2 = s.get<int32_t>(nc);
         gb_memset(cnt, 0, nc * sizeof(uint32_t));
-        unsigned g = gb_grid(v.nvals);
-        if (g > 8192) g = 8192;
+        unsigned g = gb_grid(v.nvals, GB_BLOCK, 8192);
         hipLaunchKernelGGL(k_hot_count, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), v.colidx, v.nvals, cnt);
         GB_LAUNCH_CHECK();
-        unsigned gc = gb_grid(nc);
-        if (gc > 8192) gc = 8192;
+        unsigned gc = gb_grid(nc, GB_BLOCK, 8192);
         hipLaunchKernelGGL(k_iota_i32, dim3(gc), dim3(GB_BLOCK), 0, gb_stream(), ids, nc);
         GB_LAUNCH_CHECK();
         size_t tmp = 0;
@@ -733,8 +707,8 @@ void gb_view_hot(gb_csr_view &v, GB_Obj *A, int orient) {
         gb_copy_d2d(hot, ids2, H * sizeof(int32_t));
         int32_t *rank = ids;  // reuse: -1 everywhere, then the hot ranks
         gb_memset(rank, 0xff, nc * sizeof(int32_t));
-        hipLaunchKernelGGL(k_hot_rank, dim3(std::max(1u, std::min(gb_grid(H), 8192u))), dim3(GB_BLOCK), 0,
-                           gb_stream(), hot, H, rank);
+        hipLaunchKernelGGL(k_hot_rank, dim3(gb_grid(H, GB_BLOCK, 8192)),
+                           dim3(GB_BLOCK), 0, gb_stream(), hot, H, rank);
         GB_LAUNCH_CHECK();
         int32_t *hci = gb_malloc_n<int32_t>(v.nvals);
         hipLaunchKernelGGL(k_hot_remap, dim3(g), dim3(GB_BLOCK), 0, gb_stream(), v.colidx, v.nvals, rank, hci);
@@ -759,7 +733,7 @@ __global__ void k_minmax(const T *__restrict__ x, int64_t n, long long *__restri
                          unsigned long long *__restrict__ mx_u, long long *__restrict__ mx_s) {
     long long lmn = LLONG_MAX, lmx = LLONG_MIN;
     unsigned long long umx = 0;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    GB_GRID_LOOP(i, n) {
         const T v = x[i];
         if constexpr (std::is_signed<T>::value) {
             lmn = (long long)v < lmn ? (long long)v : lmn;
@@ -787,7 +761,7 @@ __global__ void k_minmax(const T *__restrict__ x, int64_t n, long long *__restri
 
 template <class D, class T>
 __global__ void k_narrow(const T *__restrict__ x, int64_t n, D *__restrict__ y) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    GB_GRID_LOOP(i, n)
         y[i] = (D)x[i];
 }
 
@@ -805,8 +779,7 @@ void gb_view_narrow(gb_csr_view &v, GB_Obj *A, int orient) {
         long long *st = s.get<long long>(3);
         const long long init[3] = {LLONG_MAX, LLONG_MIN, 0};
         gb_copy_h2d(st, init, sizeof(init));
-        unsigned g = gb_grid(v.nvals);
-        if (g > 4096) g = 4096;
+        unsigned g = gb_grid(v.nvals, GB_BLOCK, 4096);
         gb_with_type(code, [&](auto z) {
             using T = decltype(z);
             if constexpr (std::is_integral<T>::value && sizeof(T) >= 2)

@@ -26,6 +26,7 @@
 
 #define SEL_BLOCK 256
 #define SEL_WPI 4  // keep words (64 entries each) a wave handles per iteration
+#define SEL_GRID_CAP 8192
 
 namespace {
 
@@ -54,29 +55,6 @@ GB_DEV bool sel_value(int op, X x, X y) {
     case GBAMD_IOP_VALUELT: return x < y;
     default: return x <= y;  // VALUELE
     }
-}
-
-// first index in [lo, hi] whose rowptr exceeds p (rowptr[hi] > p is known)
-GB_DEV int64_t sel_upper(const int64_t *__restrict__ rowptr, int64_t lo, int64_t hi, int64_t p) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (rowptr[mid] > p) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// first idx >= start whose rowptr exceeds p, found by the whole wave (start <= the answer, and
-// rowptr[nrows] > p, are known): lane l looks at rowptr[start + l] (returned in *mine, INT64_MAX
-// past the end), a ballot finds the answer among those 64; further away, a binary search
-GB_DEV int64_t sel_wave_upper(const int64_t *__restrict__ rowptr, int64_t start, int64_t nrows, int64_t p, int lane,
-                              int64_t *mine) {
-    const int64_t idx = start + lane;
-    const int64_t v = idx <= nrows ? rowptr[idx] : INT64_MAX;
-    *mine = v;
-    const unsigned long long b = __ballot(v > p);
-    if (b) return start + (__ffsll(b) - 1);
-    return sel_upper(rowptr, start + 64, nrows, p);
 }
 
 // words [0, nw1): nw1 = nvals / 64 + 1 covers every entry and leaves the last word's bits past
@@ -110,8 +88,8 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_select_mark(int64_t nvals, int64_
         if (MODE == SEL_ROWCOL && p0 < nvals) {
             const int64_t plast = min(p0 + SEL_WPI * 64, nvals) - 1;
             int64_t mine;
-            rlo = next < 0 ? sel_upper(rowptr, 1, nrows, p0) : sel_wave_upper(rowptr, next, nrows, p0, lane, &mine);
-            rhi = sel_wave_upper(rowptr, rlo, nrows, plast, lane, &mine);
+            rlo = next < 0 ? gb_upper_bound(rowptr, 1, nrows, p0) : gb_wave_upper(rowptr, next, nrows, p0, lane, &mine);
+            rhi = gb_wave_upper(rowptr, rlo, nrows, plast, lane, &mine);
             next = rhi;
             if (rhi - rlo < 64) {
                 nb = (int)(rhi - rlo);
@@ -119,13 +97,7 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_select_mark(int64_t nvals, int64_
             }
         }
         int below[SEL_WPI];
-#pragma unroll
-        for (int u = 0; u < SEL_WPI; u++) below[u] = 0;
-        for (int t = 0; t < nb; t++) {
-            const int r = __builtin_amdgcn_readlane(rel, t);
-#pragma unroll
-            for (int u = 0; u < SEL_WPI; u++) below[u] += r <= u * 64 + lane;
-        }
+        gb_count_bounds<SEL_WPI>(rel, 0, nb, lane, below);
         bool keep[SEL_WPI];
 #pragma unroll
         for (int u = 0; u < SEL_WPI; u++) {
@@ -137,7 +109,7 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_select_mark(int64_t nvals, int64_
                 } else {
                     const int64_t j = colidx[p];
                     int64_t i = 0;
-                    if (MODE == SEL_ROWCOL) i = (nb >= 0 ? rlo + below[u] : sel_upper(rowptr, rlo, rhi, p)) - 1;
+                    if (MODE == SEL_ROWCOL) i = (nb >= 0 ? rlo + below[u] : gb_upper_bound(rowptr, rlo, rhi, p)) - 1;
                     kp = sel_positional(op, i, j, k);
                 }
             }
@@ -156,25 +128,12 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_select_mark(int64_t nvals, int64_
 
 // VS: bytes per value, 0 = no values to move (iso)
 template <int VS>
-struct sel_word;
-template <>
-struct sel_word<0> { using type = uint8_t; };
-template <>
-struct sel_word<1> { using type = uint8_t; };
-template <>
-struct sel_word<2> { using type = uint16_t; };
-template <>
-struct sel_word<4> { using type = uint32_t; };
-template <>
-struct sel_word<8> { using type = uint64_t; };
-
-template <int VS>
 __global__ __launch_bounds__(SEL_BLOCK) void k_select_scatter(int64_t nw, const uint64_t *__restrict__ words,
                                                               const int64_t *__restrict__ base,
                                                               const int32_t *__restrict__ colidx,
                                                               const void *__restrict__ vals_,
                                                               int32_t *__restrict__ ocol, void *__restrict__ ovals_) {
-    using V = typename sel_word<VS>::type;
+    using V = gb_word_t<VS>;
     const V *__restrict__ vals = (const V *)vals_;
     V *__restrict__ ovals = (V *)ovals_;
     const int lane = threadIdx.x & 63;
@@ -201,7 +160,7 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_select_rowptr(int64_t nrows, cons
                                                              const uint64_t *__restrict__ words,
                                                              const int64_t *__restrict__ base,
                                                              int64_t *__restrict__ orowptr) {
-    for (int64_t i = blockIdx.x * (int64_t)SEL_BLOCK + threadIdx.x; i <= nrows; i += (int64_t)gridDim.x * SEL_BLOCK) {
+    GB_GRID_LOOP(i, nrows + 1) {
         const int64_t r = rowptr[i];
         const int64_t w = r >> 6;  // at most nvals >> 6: the word after the last exists and is zero
         orowptr[i] = base[w] + __popcll(words[w] & ((1ull << (r & 63)) - 1));
@@ -228,21 +187,11 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_select_vec(int64_t n, int64_t nw,
     }
 }
 
-unsigned sel_grid(int64_t nwaves_wanted) {
-    int64_t g = (nwaves_wanted + SEL_BLOCK / 64 - 1) / (SEL_BLOCK / 64);
-    return (unsigned)std::min<int64_t>(std::max<int64_t>(g, 1), 8192);
-}
-
-// the thunk *y (type ycode) cast to T
+// the thunk *y (type ycode) cast to T, the type of code tcode
 template <class T>
-T sel_thunk(const void *y, int ycode) {
+T sel_thunk(const void *y, int ycode, int tcode) {
     T out = T();
-    gb_with_type(ycode, [&](auto sv) {
-        using S = decltype(sv);
-        S v;
-        memcpy(&v, y, sizeof(S));
-        out = gb_cast<T, S>(v);
-    });
+    gb_cast_scalar(&out, tcode, y, ycode);
     return out;
 }
 
@@ -250,7 +199,7 @@ T sel_thunk(const void *y, int ycode) {
 // the clamp keeps i + k from overflowing
 int64_t sel_thunk_k(const void *y, int ycode) {
     const int64_t lim = (int64_t)1 << 61;
-    return std::min(std::max(sel_thunk<int64_t>(y, ycode), -lim), lim);
+    return std::min(std::max(sel_thunk<int64_t>(y, ycode, GBAMD_T_INT64), -lim), lim);
 }
 
 void select_vector(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_IndexUnaryOp op, GB_Obj *A, const void *y, int ycode,
@@ -261,16 +210,10 @@ void select_vector(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_IndexUnaryOp op
     gb_get_bitmap(uv, A);
     const size_t vs = gb_type_size(uv.tcode);
     const int64_t nw = gb_words(uv.n);
-    gb_vec_result T;
-    T.n = uv.n;
-    T.tcode = uv.tcode;
-    T.iso = uv.iso;
-    T.bits = gb_malloc_n<uint64_t>(std::max<int64_t>(nw, 1));
+    gb_vec_result T = gb_new_vec_result(uv.n, uv.tcode, uv.iso);
     const int64_t nv = uv.iso ? 1 : uv.n;
-    T.dense = gb_malloc(std::max<int64_t>(nv, 1) * vs);
-    T.d_nvals = gb_malloc_n<int64_t>(1);
     if (nw) {
-        const unsigned grid = sel_grid(nw);
+        const unsigned grid = gb_grid(nw, SEL_BLOCK / 64, SEL_GRID_CAP);
         if (op->xtype) {
             gb_scratch s;
             const void *xin = gb_bitmap_vals_as(uv, op->xtype->code, s);
@@ -278,7 +221,7 @@ void select_vector(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_IndexUnaryOp op
                 using X = decltype(xv);
                 hipLaunchKernelGGL((k_select_vec<true, X>), dim3(grid), dim3(SEL_BLOCK), 0, gb_stream(), uv.n, nw,
                                    op->opcode, uv.bits, (const X *)xin, uv.iso, (int64_t)0,
-                                   sel_thunk<X>(y, ycode), T.bits);
+                                   sel_thunk<X>(y, ycode, op->xtype->code), T.bits);
             });
         } else {
             hipLaunchKernelGGL((k_select_vec<false, int64_t>), dim3(grid), dim3(SEL_BLOCK), 0, gb_stream(), uv.n, nw,
@@ -315,14 +258,14 @@ void select_matrix(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_IndexUnaryOp op
         uint8_t *cnt = s.get<uint8_t>(nw1);
         base = s.get<int64_t>(nw1 + 1);
         // a wave takes a run of chunks (4 or more, once there are that many)
-        const unsigned grid = sel_grid(((nw1 + SEL_WPI - 1) / SEL_WPI + 3) / 4);
+        const unsigned grid = gb_grid(((nw1 + SEL_WPI - 1) / SEL_WPI + 3) / 4, SEL_BLOCK / 64, SEL_GRID_CAP);
         if (op->xtype) {
             const void *xin = gb_view_vals_as(v, op->xtype->code, s);
             gb_with_type(op->xtype->code, [&](auto xv) {
                 using X = decltype(xv);
                 hipLaunchKernelGGL((k_select_mark<SEL_VALUE, X>), dim3(grid), dim3(SEL_BLOCK), 0, gb_stream(),
                                    v.nvals, v.nrows, nw1, op->opcode, v.rowptr, v.colidx, (const X *)xin, v.iso,
-                                   (int64_t)0, sel_thunk<X>(y, ycode), words, cnt);
+                                   (int64_t)0, sel_thunk<X>(y, ycode, op->xtype->code), words, cnt);
             });
         } else {
             const int64_t k = sel_thunk_k(y, ycode);
@@ -355,23 +298,17 @@ void select_matrix(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_IndexUnaryOp op
         gb_copy_d2d(T.vals, v.vals, nv * vs);
     } else {
         const int64_t nw = gb_words(v.nvals);
-        const unsigned grid = sel_grid((nw + SEL_WPI - 1) / SEL_WPI);
-        const int VS = v.iso ? 0 : (int)vs;
-#define SEL_SCATTER(N)                                                                                          \
-    hipLaunchKernelGGL((k_select_scatter<N>), dim3(grid), dim3(SEL_BLOCK), 0, gb_stream(), nw, words, base,      \
-                       v.colidx, v.vals, T.colidx, T.vals)
-        switch (VS) {
-        case 0: SEL_SCATTER(0); break;
-        case 1: SEL_SCATTER(1); break;
-        case 2: SEL_SCATTER(2); break;
-        case 4: SEL_SCATTER(4); break;
-        default: SEL_SCATTER(8); break;
-        }
-#undef SEL_SCATTER
+        const unsigned grid = gb_grid((nw + SEL_WPI - 1) / SEL_WPI, SEL_BLOCK / 64, SEL_GRID_CAP);
+        auto scatter = [&](auto vsize) {
+            hipLaunchKernelGGL((k_select_scatter<decltype(vsize)::value>), dim3(grid), dim3(SEL_BLOCK), 0, gb_stream(),
+                               nw, words, base, v.colidx, v.vals, T.colidx, T.vals);
+        };
+        if (v.iso) scatter(std::integral_constant<int, 0>{});
+        else gb_with_size(vs, [&](auto w) { scatter(std::integral_constant<int, (int)sizeof(w)>{}); });
         GB_LAUNCH_CHECK();
         if (v.iso) gb_copy_d2d(T.vals, v.vals, vs);
-        hipLaunchKernelGGL(k_select_rowptr, dim3(sel_grid((v.nrows + 1 + 63) / 64)), dim3(SEL_BLOCK), 0, gb_stream(),
-                           v.nrows, v.rowptr, words, base, T.rowptr);
+        hipLaunchKernelGGL(k_select_rowptr, dim3(gb_grid((v.nrows + 1 + 63) / 64, SEL_BLOCK / 64, SEL_GRID_CAP)),
+                           dim3(SEL_BLOCK), 0, gb_stream(), v.nrows, v.rowptr, words, base, T.rowptr);
         GB_LAUNCH_CHECK();
     }
     gb_writeback_matrix(C, T, M, d, accum);
@@ -383,7 +320,7 @@ void gb_select(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_IndexUnaryOp op, GB
                const gb_desc &d) {
     GB_REQUIRE(op, GrB_NULL_POINTER, "operator is NULL");
     GB_REQUIRE(op->magic == GB_MAGIC, GrB_UNINITIALIZED_OBJECT, "invalid operator");
-    if (accum) GB_REQUIRE(accum->magic == GB_MAGIC, GrB_UNINITIALIZED_OBJECT, "invalid operator");
+    gb_check_binop(accum, true);
     GB_REQUIRE(op->opcode >= 0 && op->opcode < GBAMD_IOP_COUNT, GrB_INVALID_VALUE, "unknown index-unary operator");
     if (C->kind != GB_KIND_MATRIX) select_vector(C, M, accum, op, A, y, ycode, d);
     else select_matrix(C, M, accum, op, A, y, ycode, d);

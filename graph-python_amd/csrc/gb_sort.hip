@@ -317,12 +317,6 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_sort_all_emit(sort_args a, const
     }
 }
 
-unsigned sort_grid(int64_t blocks, int64_t cap = 8192) {
-    const int64_t k = gb_knob("sort_grid");  // tests: few blocks, so that every stride loop runs
-    if (k > 0 && k < cap) cap = k;
-    return (unsigned)std::min<int64_t>(std::max<int64_t>(blocks, 1), cap);
-}
-
 // rows per class of the last matrix sort, on the device: read only when a counter is asked for
 unsigned long long *g_sort_stats = nullptr;
 
@@ -330,6 +324,10 @@ int sort_knob(const char *key, int dflt) {
     const int64_t k = gb_knob(key);
     return k > 0 && k < dflt ? (int)k : dflt;
 }
+
+// the cap on a launch's blocks; the knob sort_grid lowers it (tests: few blocks, so that every
+// stride loop runs)
+int64_t sort_cap(int cap = 8192) { return sort_knob("sort_grid", cap); }
 
 // LT or GT over one type with a BOOL result; returns the operator's type code
 int sort_check_op(GrB_BinaryOp op, bool *desc) {
@@ -358,11 +356,11 @@ void sort_segments(sort_args &a, int xcode, int key_bits, int64_t nseg, const in
     gb_with_type(xcode, [&](auto xv) {
         using X = decltype(xv);
         if (a.all_long)
-            hipLaunchKernelGGL((k_sort_all_keys<X, K>), dim3(sort_grid((a.nvals + SORT_BLOCK - 1) / SORT_BLOCK)),
+            hipLaunchKernelGGL((k_sort_all_keys<X, K>), dim3(gb_grid(a.nvals, SORT_BLOCK, sort_cap())),
                                dim3(SORT_BLOCK), 0, gb_stream(), a, kin, pin);
         else
-            hipLaunchKernelGGL((k_sort_long_keys<X, K>), dim3(sort_grid(nseg)), dim3(SORT_BLOCK), 0, gb_stream(), a,
-                               kin, pin);
+            hipLaunchKernelGGL((k_sort_long_keys<X, K>), dim3(gb_grid(nseg, 1, sort_cap())), dim3(SORT_BLOCK), 0,
+                               gb_stream(), a, kin, pin);
     });
     GB_LAUNCH_CHECK();
     size_t tmp = 0;
@@ -372,10 +370,10 @@ void sort_segments(sort_args &a, int xcode, int key_bits, int64_t nseg, const in
     GB_HIP(hipcub::DeviceSegmentedRadixSort::SortPairs(t, tmp, (const K *)kin, kout, (const uint32_t *)pin, pout,
                                                        (int)a.nvals, (int)nseg, beg, end, 0, key_bits, gb_stream()));
     if (a.all_long)
-        hipLaunchKernelGGL(k_sort_all_emit, dim3(sort_grid((a.nvals + SORT_BLOCK - 1) / SORT_BLOCK)), dim3(SORT_BLOCK),
+        hipLaunchKernelGGL(k_sort_all_emit, dim3(gb_grid(a.nvals, SORT_BLOCK, sort_cap())), dim3(SORT_BLOCK),
                            0, gb_stream(), a, (const uint32_t *)pout);
     else
-        hipLaunchKernelGGL(k_sort_long_emit, dim3(sort_grid(nseg)), dim3(SORT_BLOCK), 0, gb_stream(), a,
+        hipLaunchKernelGGL(k_sort_long_emit, dim3(gb_grid(nseg, 1, sort_cap())), dim3(SORT_BLOCK), 0, gb_stream(), a,
                            (const uint32_t *)pout);
     GB_LAUNCH_CHECK();
 }
@@ -403,14 +401,7 @@ void matrix_sort(GB_Obj *C, GB_Obj *P, GrB_BinaryOp op, GB_Obj *A, const gb_desc
     if (nv == 0) {
         for (GB_Obj *O : {C, P}) {
             if (!O) continue;
-            gb_mat_result T;
-            T.nrows = O->nrows;
-            T.ncols = gb_ncols_of(O);
-            T.tcode = O->type->code;
-            T.rowptr = gb_malloc_n<int64_t>(T.nrows + 1);
-            gb_memset(T.rowptr, 0, (T.nrows + 1) * sizeof(int64_t));
-            T.colidx = gb_malloc_n<int32_t>(1);
-            T.vals = gb_malloc(8);
+            gb_mat_result T = gb_empty_mat_result(O->nrows, gb_ncols_of(O), O->type->code);
             gb_writeback_matrix(O, T, nullptr, d0, nullptr);
         }
         return;
@@ -434,7 +425,7 @@ void matrix_sort(GB_Obj *C, GB_Obj *P, GrB_BinaryOp op, GB_Obj *A, const gb_desc
         a.stats = g_sort_stats;
         if (v.iso) {
             if (C) gb_copy_d2d(cvals, v.vals, vs);
-            hipLaunchKernelGGL(k_sort_all_emit, dim3(sort_grid((nv + SORT_BLOCK - 1) / SORT_BLOCK)), dim3(SORT_BLOCK), 0,
+            hipLaunchKernelGGL(k_sort_all_emit, dim3(gb_grid(nv, SORT_BLOCK, sort_cap())), dim3(SORT_BLOCK), 0,
                                gb_stream(), a, (const uint32_t *)nullptr);
             GB_LAUNCH_CHECK();
         } else {
@@ -455,14 +446,14 @@ void matrix_sort(GB_Obj *C, GB_Obj *P, GrB_BinaryOp op, GB_Obj *A, const gb_desc
             if (a.capL) gb_memset(a.lbeg, 0, 2 * a.capL * sizeof(int64_t));
             gb_with_type(xcode, [&](auto xv) {
                 using X = decltype(xv);
-                hipLaunchKernelGGL(k_sort_wave<X>, dim3(sort_grid((v.nrows + 255) / 256)), dim3(SORT_BLOCK), 0,
+                hipLaunchKernelGGL(k_sort_wave<X>, dim3(gb_grid(v.nrows, 256, sort_cap())), dim3(SORT_BLOCK), 0,
                                    gb_stream(), a);
                 if (a.capB)
-                    hipLaunchKernelGGL((k_sort_block<X, SORT_SMALL_CAP, 64>), dim3(sort_grid(a.capB)), dim3(64), 0,
-                                       gb_stream(), a);
+                    hipLaunchKernelGGL((k_sort_block<X, SORT_SMALL_CAP, 64>), dim3(gb_grid(a.capB, 1, sort_cap())),
+                                       dim3(64), 0, gb_stream(), a);
                 if (a.capB2)
-                    hipLaunchKernelGGL((k_sort_block<X, SORT_BLOCK_CAP, SORT_BLOCK>), dim3(sort_grid(a.capB2, 4096)),
-                                       dim3(SORT_BLOCK), 0, gb_stream(), a);
+                    hipLaunchKernelGGL((k_sort_block<X, SORT_BLOCK_CAP, SORT_BLOCK>),
+                                       dim3(gb_grid(a.capB2, 1, sort_cap(4096))), dim3(SORT_BLOCK), 0, gb_stream(), a);
             });
             GB_LAUNCH_CHECK();
             if (a.all_long || a.capL) {
@@ -514,7 +505,7 @@ void matrix_sort(GB_Obj *C, GB_Obj *P, GrB_BinaryOp op, GB_Obj *A, const gb_desc
 
 // ------------------------------------------------------------------ vectors
 __global__ void k_sort_vec_pop(const uint64_t *__restrict__ bits, int64_t n, int64_t nw, int64_t *__restrict__ pop) {
-    for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w < nw; w += (int64_t)gridDim.x * blockDim.x) {
+    GB_GRID_LOOP(w, nw) {
         uint64_t b = bits[w];
         if (w == nw - 1 && (n & 63)) b &= (1ull << (n & 63)) - 1;
         pop[w] = __popcll(b);
@@ -591,21 +582,8 @@ void vector_sort(GB_Obj *W, GB_Obj *P, GrB_BinaryOp op, GB_Obj *U) {
     const int64_t n = uv.n, nw = gb_words(n);
     const size_t vs = gb_type_size(uv.tcode);
     gb_vec_result TW, TP;
-    if (W) {
-        TW.n = n;
-        TW.tcode = uv.tcode;
-        TW.iso = uv.iso;
-        TW.bits = gb_malloc_n<uint64_t>(std::max<int64_t>(nw, 1));
-        TW.dense = gb_malloc(std::max<int64_t>(uv.iso ? 1 : n, 1) * vs);
-        TW.d_nvals = gb_malloc_n<int64_t>(1);
-    }
-    if (P) {
-        TP.n = n;
-        TP.tcode = P->type->code;
-        TP.bits = gb_malloc_n<uint64_t>(std::max<int64_t>(nw, 1));
-        TP.dense = gb_malloc(std::max<int64_t>(n, 1) * sizeof(int64_t));
-        TP.d_nvals = gb_malloc_n<int64_t>(1);
-    }
+    if (W) TW = gb_new_vec_result(n, uv.tcode, uv.iso);
+    if (P) TP = gb_new_vec_result(n, P->type->code, false);  // INT64 or UINT64: checked above
     if (n == 0) {
         if (W) gb_memset(TW.d_nvals, 0, sizeof(int64_t));
         if (P) gb_memset(TP.d_nvals, 0, sizeof(int64_t));
@@ -614,9 +592,9 @@ void vector_sort(GB_Obj *W, GB_Obj *P, GrB_BinaryOp op, GB_Obj *U) {
         int64_t *pop = s.get<int64_t>(nw), *off = s.get<int64_t>(nw + 1);
         uint64_t *keys = s.get<uint64_t>(n);
         int64_t *idx = s.get<int64_t>(n);
-        const unsigned grid = sort_grid((n + SORT_BLOCK - 1) / SORT_BLOCK);
-        hipLaunchKernelGGL(k_sort_vec_pop, dim3(sort_grid((nw + 255) / 256)), dim3(256), 0, gb_stream(), uv.bits, n, nw,
-                           pop);
+        const unsigned grid = gb_grid(n, SORT_BLOCK, sort_cap());
+        hipLaunchKernelGGL(k_sort_vec_pop, dim3(gb_grid(nw, 256, sort_cap())), dim3(256), 0, gb_stream(), uv.bits, n,
+                           nw, pop);
         GB_LAUNCH_CHECK();
         gb_exclusive_scan_i64(pop, off, nw);
         const int key_bits = 8 * (int)gb_type_size(xcode);

@@ -18,20 +18,13 @@
 #include "gb_internal.h"
 
 #define WB_BLOCK 256
-static inline unsigned wb_grid(int64_t n, unsigned cap = 16384) {
-    int64_t g = (n + WB_BLOCK - 1) / WB_BLOCK;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
-}
-#define WB_STRIDE(i, n) \
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
+#define WB_GRID_CAP 16384  // blocks, unless the launch names its own cap
 
 // ================================================================== masks
 template <class T>
 __global__ void k_vmask_values(const uint64_t *__restrict__ bits, const T *__restrict__ vals, bool iso, int64_t n,
                                uint64_t *__restrict__ out) {
-    WB_STRIDE(w, (n + 63) >> 6) {
+    GB_GRID_LOOP(w, (n + 63) >> 6) {
         uint64_t word = bits[w], r = 0;
         while (word) {
             int b = __ffsll((unsigned long long)word) - 1;
@@ -76,8 +69,8 @@ void gb_make_vmask(gb_vmask &m, GB_Obj *M, const gb_desc &d, int64_t n, bool all
         uint64_t *c = m.own.get<uint64_t>(gb_words(n));
         gb_with_type(bv->tcode, [&](auto z) {
             using T = decltype(z);
-            hipLaunchKernelGGL(k_vmask_values<T>, dim3(wb_grid(gb_words(n))), dim3(WB_BLOCK), 0, gb_stream(), bv->bits,
-                               (const T *)bv->vals, bv->iso, n, c);
+            hipLaunchKernelGGL(k_vmask_values<T>, dim3(gb_grid(gb_words(n), WB_BLOCK, WB_GRID_CAP)), dim3(WB_BLOCK), 0,
+                               gb_stream(), bv->bits, (const T *)bv->vals, bv->iso, n, c);
         });
         GB_LAUNCH_CHECK();
         m.bits = c;
@@ -88,7 +81,7 @@ void gb_make_vmask(gb_vmask &m, GB_Obj *M, const gb_desc &d, int64_t n, bool all
 template <class T>
 __global__ void k_mmask_count(const int64_t *__restrict__ rp, const T *__restrict__ vals, bool iso, int64_t nrows,
                               int64_t *__restrict__ cnt) {
-    WB_STRIDE(i, nrows) {
+    GB_GRID_LOOP(i, nrows) {
         int64_t c = 0;
         for (int64_t p = rp[i]; p < rp[i + 1]; p++) c += gb_cast<bool, T>(iso ? vals[0] : vals[p]);
         cnt[i] = c;
@@ -97,7 +90,7 @@ __global__ void k_mmask_count(const int64_t *__restrict__ rp, const T *__restric
 template <class T>
 __global__ void k_mmask_fill(const int64_t *__restrict__ rp, const int32_t *__restrict__ ci, const T *__restrict__ vals,
                              bool iso, int64_t nrows, const int64_t *__restrict__ rp2, int32_t *__restrict__ ci2) {
-    WB_STRIDE(i, nrows) {
+    GB_GRID_LOOP(i, nrows) {
         int64_t o = rp2[i];
         for (int64_t p = rp[i]; p < rp[i + 1]; p++)
             if (gb_cast<bool, T>(iso ? vals[0] : vals[p])) ci2[o++] = ci[p];
@@ -135,8 +128,8 @@ void gb_make_mmask(gb_mmask &m, GB_Obj *M, const gb_desc &d, int64_t nrows, int6
     gb_with_type(m.view.tcode, [&](auto z) {
         using T = decltype(z);
         if (nrows)
-            hipLaunchKernelGGL(k_mmask_count<T>, dim3(wb_grid(nrows)), dim3(WB_BLOCK), 0, gb_stream(), m.view.rowptr,
-                               (const T *)m.view.vals, m.view.iso, nrows, cnt);
+            hipLaunchKernelGGL(k_mmask_count<T>, dim3(gb_grid(nrows, WB_BLOCK, WB_GRID_CAP)), dim3(WB_BLOCK), 0,
+                               gb_stream(), m.view.rowptr, (const T *)m.view.vals, m.view.iso, nrows, cnt);
     });
     GB_LAUNCH_CHECK();
     gb_exclusive_scan_i64(cnt, rp2, nrows);
@@ -145,8 +138,9 @@ void gb_make_mmask(gb_mmask &m, GB_Obj *M, const gb_desc &d, int64_t nrows, int6
     gb_with_type(m.view.tcode, [&](auto z) {
         using T = decltype(z);
         if (nrows)
-            hipLaunchKernelGGL(k_mmask_fill<T>, dim3(wb_grid(nrows)), dim3(WB_BLOCK), 0, gb_stream(), m.view.rowptr,
-                               m.view.colidx, (const T *)m.view.vals, m.view.iso, nrows, rp2, ci2);
+            hipLaunchKernelGGL(k_mmask_fill<T>, dim3(gb_grid(nrows, WB_BLOCK, WB_GRID_CAP)), dim3(WB_BLOCK), 0,
+                               gb_stream(), m.view.rowptr, m.view.colidx, (const T *)m.view.vals, m.view.iso, nrows,
+                               rp2, ci2);
     });
     GB_LAUNCH_CHECK();
     m.rowptr = rp2;
@@ -213,7 +207,7 @@ template <class CT>
 __global__ __launch_bounds__(WB_BLOCK) void k_vec_restore(int64_t n, const uint64_t *__restrict__ kbits,
                                                           const CT *__restrict__ cvals, bool c_iso,
                                                           CT *__restrict__ ovals) {
-    WB_STRIDE(i, n) {
+    GB_GRID_LOOP(i, n) {
         if (gb_bit(kbits, i)) ovals[i] = cvals[c_iso ? 0 : i];
     }
 }
@@ -286,9 +280,9 @@ bool gb_writeback_vector(GB_Obj *C, gb_vec_result &T, GB_Obj *M, const gb_desc &
     if (n) {
         gb_with_type(wcode, [&](auto z) {
             using W = decltype(z);
-            hipLaunchKernelGGL(k_vec_merge<W>, dim3(wb_grid(n, 1024)), dim3(WB_BLOCK), 0, gb_stream(), n, cv.bits,
-                               (const W *)cvals, c_iso, T.bits, (const W *)T.dense, T.iso, mask.bits, mask.comp,
-                               d.replace, accum ? accum->opcode : -1, obits, (W *)ovals, kbits,
+            hipLaunchKernelGGL(k_vec_merge<W>, dim3(gb_grid(n, WB_BLOCK, 1024)), dim3(WB_BLOCK), 0, gb_stream(), n,
+                               cv.bits, (const W *)cvals, c_iso, T.bits, (const W *)T.dense, T.iso, mask.bits,
+                               mask.comp, d.replace, accum ? accum->opcode : -1, obits, (W *)ovals, kbits,
                                (unsigned long long *)cnt, gb_device_state());
         });
         GB_LAUNCH_CHECK();
@@ -302,11 +296,11 @@ bool gb_writeback_vector(GB_Obj *C, gb_vec_result &T, GB_Obj *M, const gb_desc &
         if (n) {
             gb_with_type(ct, [&](auto z) {
                 using CT = decltype(z);
-                hipLaunchKernelGGL(k_vec_restore<CT>, dim3(wb_grid(n, 1024)), dim3(WB_BLOCK), 0, gb_stream(), n, kbits,
-                                   (const CT *)cv.vals, cv.iso, (CT *)ovals);
+                hipLaunchKernelGGL(k_vec_restore<CT>, dim3(gb_grid(n, WB_BLOCK, 1024)), dim3(WB_BLOCK), 0, gb_stream(),
+                                   n, kbits, (const CT *)cv.vals, cv.iso, (CT *)ovals);
                 if (t_direct)
-                    hipLaunchKernelGGL(k_vec_restore<CT>, dim3(wb_grid(n, 1024)), dim3(WB_BLOCK), 0, gb_stream(), n,
-                                       kbits + gb_words(n), (const CT *)t_direct, t_iso, (CT *)ovals);
+                    hipLaunchKernelGGL(k_vec_restore<CT>, dim3(gb_grid(n, WB_BLOCK, 1024)), dim3(WB_BLOCK), 0,
+                                       gb_stream(), n, kbits + gb_words(n), (const CT *)t_direct, t_iso, (CT *)ovals);
             });
             GB_LAUNCH_CHECK();
         }
@@ -327,28 +321,15 @@ bool gb_writeback_vector(GB_Obj *C, gb_vec_result &T, GB_Obj *M, const gb_desc &
 // A C entry survives where the mask is false (unless replace) or where it is true,
 // accum is set and T has no entry; a T entry survives where the mask is true and
 // carries accum(C, T) when C has the entry too.
+// the row of entry e < rp[nrows]: the last r with rp[r] <= e
 __device__ __forceinline__ int64_t wb_row_of(const int64_t *__restrict__ rp, int64_t nrows, int64_t e) {
-    int64_t lo = 0, hi = nrows;  // last r with rp[r] <= e
-    while (hi - lo > 1) {
-        int64_t mid = (lo + hi) >> 1;
-        if (rp[mid] <= e) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-__device__ __forceinline__ int64_t wb_lower_bound(const int32_t *__restrict__ ci, int64_t lo, int64_t hi, int32_t j) {
-    while (lo < hi) {
-        int64_t mid = (lo + hi) >> 1;
-        if (ci[mid] < j) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
+    return gb_upper_bound(rp, 1, nrows, e) - 1;
 }
 __device__ __forceinline__ bool wb_mask_at(const int64_t *__restrict__ mrp, const int32_t *__restrict__ mci,
                                           bool has_mask, bool mcomp, int64_t r, int32_t j) {
     if (!has_mask) return !mcomp;
     int64_t a = mrp[r], b = mrp[r + 1];
-    int64_t p = wb_lower_bound(mci, a, b, j);
+    int64_t p = gb_lower_bound(mci, a, b, j);
     return (p < b && mci[p] == j) != mcomp;
 }
 
@@ -357,14 +338,14 @@ __global__ __launch_bounds__(WB_BLOCK) void k_merge_flag_c(
     const int64_t *__restrict__ trp, const int32_t *__restrict__ tci, const int64_t *__restrict__ mrp,
     const int32_t *__restrict__ mci, bool has_mask, bool mcomp, bool replace, bool accum,
     uint8_t *__restrict__ flag) {
-    WB_STRIDE(e, cnz) {
+    GB_GRID_LOOP(e, cnz) {
         const int64_t r = wb_row_of(crp, nrows, e);
         const int32_t j = cci[e];
         bool keep;
         if (wb_mask_at(mrp, mci, has_mask, mcomp, r, j)) {
             if (accum) {
                 int64_t a = trp[r], b = trp[r + 1];
-                int64_t p = wb_lower_bound(tci, a, b, j);
+                int64_t p = gb_lower_bound(tci, a, b, j);
                 keep = !(p < b && tci[p] == j);
             } else {
                 keep = false;
@@ -380,7 +361,7 @@ __global__ __launch_bounds__(WB_BLOCK) void k_merge_flag_t(
     int64_t nrows, int64_t tnz, const int64_t *__restrict__ trp, const int32_t *__restrict__ tci,
     const int64_t *__restrict__ mrp, const int32_t *__restrict__ mci, bool has_mask, bool mcomp, bool within_mask,
     uint8_t *__restrict__ flag) {
-    WB_STRIDE(e, tnz) {
+    GB_GRID_LOOP(e, tnz) {
         bool keep = true;
         if (!within_mask) {
             const int64_t r = wb_row_of(trp, nrows, e);
@@ -393,7 +374,7 @@ __global__ __launch_bounds__(WB_BLOCK) void k_merge_flag_t(
 __global__ void k_merge_rowptr(int64_t nrows, const int64_t *__restrict__ crp, const int64_t *__restrict__ trp,
                                const int64_t *__restrict__ sc, const int64_t *__restrict__ st,
                                int64_t *__restrict__ orp) {
-    WB_STRIDE(r, nrows + 1) orp[r] = sc[crp[r]] + st[trp[r]];
+    GB_GRID_LOOP(r, nrows + 1) orp[r] = sc[crp[r]] + st[trp[r]];
 }
 
 template <class CT>
@@ -402,11 +383,11 @@ __global__ __launch_bounds__(WB_BLOCK) void k_merge_place_c(
     const CT *__restrict__ cvx, bool c_iso, const int64_t *__restrict__ trp, const int32_t *__restrict__ tci,
     const int64_t *__restrict__ sc, const int64_t *__restrict__ st, int32_t *__restrict__ oci,
     CT *__restrict__ ovx) {
-    WB_STRIDE(e, cnz) {
+    GB_GRID_LOOP(e, cnz) {
         if (sc[e + 1] == sc[e]) continue;
         const int64_t r = wb_row_of(crp, nrows, e);
         const int32_t j = cci[e];
-        const int64_t p = wb_lower_bound(tci, trp[r], trp[r + 1], j);
+        const int64_t p = gb_lower_bound(tci, trp[r], trp[r + 1], j);
         const int64_t o = sc[e] + st[p];
         oci[o] = j;
         ovx[o] = cvx[c_iso ? 0 : e];
@@ -419,12 +400,12 @@ __global__ __launch_bounds__(WB_BLOCK) void k_merge_place_t(
     const CT *__restrict__ tvx, bool t_iso, const int64_t *__restrict__ crp, const int32_t *__restrict__ cci,
     const CT *__restrict__ cvx, bool c_iso, int accum, const int64_t *__restrict__ sc,
     const int64_t *__restrict__ st, int32_t *__restrict__ oci, CT *__restrict__ ovx) {
-    WB_STRIDE(e, tnz) {
+    GB_GRID_LOOP(e, tnz) {
         if (st[e + 1] == st[e]) continue;
         const int64_t r = wb_row_of(trp, nrows, e);
         const int32_t j = tci[e];
         const int64_t a = crp[r], b = crp[r + 1];
-        const int64_t p = wb_lower_bound(cci, a, b, j);
+        const int64_t p = gb_lower_bound(cci, a, b, j);
         const bool hit = p < b && cci[p] == j;
         if (accum == -2 && hit) continue;  // restore pass: only the entries C does not hold
         CT v = tvx[t_iso ? 0 : e];
@@ -492,19 +473,19 @@ void gb_writeback_matrix(GB_Obj *C, gb_mat_result &T, GB_Obj *M, const gb_desc &
     int64_t *sc = s.get<int64_t>(cnz + 1);
     int64_t *st = s.get<int64_t>(tnz + 1);
     if (cnz)
-        hipLaunchKernelGGL(k_merge_flag_c, dim3(wb_grid(cnz)), dim3(WB_BLOCK), 0, gb_stream(), nrows, cnz, cv.rowptr,
-                           cv.colidx, T.rowptr, T.colidx, mask.rowptr, mask.colidx, has_mask, mask.comp, d.replace,
-                           accum != nullptr, fc);
+        hipLaunchKernelGGL(k_merge_flag_c, dim3(gb_grid(cnz, WB_BLOCK, WB_GRID_CAP)), dim3(WB_BLOCK), 0, gb_stream(),
+                           nrows, cnz, cv.rowptr, cv.colidx, T.rowptr, T.colidx, mask.rowptr, mask.colidx, has_mask,
+                           mask.comp, d.replace, accum != nullptr, fc);
     if (tnz)
-        hipLaunchKernelGGL(k_merge_flag_t, dim3(wb_grid(tnz)), dim3(WB_BLOCK), 0, gb_stream(), nrows, tnz, T.rowptr,
-                           T.colidx, mask.rowptr, mask.colidx, has_mask, mask.comp,
+        hipLaunchKernelGGL(k_merge_flag_t, dim3(gb_grid(tnz, WB_BLOCK, WB_GRID_CAP)), dim3(WB_BLOCK), 0, gb_stream(),
+                           nrows, tnz, T.rowptr, T.colidx, mask.rowptr, mask.colidx, has_mask, mask.comp,
                            T.within_mask && has_mask && !mask.comp, ft);
     GB_LAUNCH_CHECK();
     gb_exclusive_scan_u8(fc, sc, cnz);
     gb_exclusive_scan_u8(ft, st, tnz);
     int64_t *orp = gb_malloc_n<int64_t>(nrows + 1);
-    hipLaunchKernelGGL(k_merge_rowptr, dim3(wb_grid(nrows + 1)), dim3(WB_BLOCK), 0, gb_stream(), nrows, cv.rowptr,
-                       T.rowptr, sc, st, orp);
+    hipLaunchKernelGGL(k_merge_rowptr, dim3(gb_grid(nrows + 1, WB_BLOCK, WB_GRID_CAP)), dim3(WB_BLOCK), 0, gb_stream(),
+                       nrows, cv.rowptr, T.rowptr, sc, st, orp);
     GB_LAUNCH_CHECK();
     int64_t nz = gb_read_i64(orp + nrows);
     int32_t *oci = gb_malloc_n<int32_t>(std::max<int64_t>(nz, 1));
@@ -512,13 +493,13 @@ void gb_writeback_matrix(GB_Obj *C, gb_mat_result &T, GB_Obj *M, const gb_desc &
     gb_with_type(wcode, [&](auto z) {
         using W = decltype(z);
         if (cnz)
-            hipLaunchKernelGGL((k_merge_place_c<W>), dim3(wb_grid(cnz)), dim3(WB_BLOCK), 0, gb_stream(), nrows, cnz,
-                               cv.rowptr, cv.colidx, (const W *)cvals, cv.iso, T.rowptr, T.colidx, sc, st, oci,
-                               (W *)ovx);
+            hipLaunchKernelGGL((k_merge_place_c<W>), dim3(gb_grid(cnz, WB_BLOCK, WB_GRID_CAP)), dim3(WB_BLOCK), 0,
+                               gb_stream(), nrows, cnz, cv.rowptr, cv.colidx, (const W *)cvals, cv.iso, T.rowptr,
+                               T.colidx, sc, st, oci, (W *)ovx);
         if (tnz)
-            hipLaunchKernelGGL((k_merge_place_t<W>), dim3(wb_grid(tnz)), dim3(WB_BLOCK), 0, gb_stream(), nrows, tnz,
-                               T.rowptr, T.colidx, (const W *)T.vals, T.iso, cv.rowptr, cv.colidx, (const W *)cvals,
-                               cv.iso, accum ? accum->opcode : -1, sc, st, oci, (W *)ovx);
+            hipLaunchKernelGGL((k_merge_place_t<W>), dim3(gb_grid(tnz, WB_BLOCK, WB_GRID_CAP)), dim3(WB_BLOCK), 0,
+                               gb_stream(), nrows, tnz, T.rowptr, T.colidx, (const W *)T.vals, T.iso, cv.rowptr,
+                               cv.colidx, (const W *)cvals, cv.iso, accum ? accum->opcode : -1, sc, st, oci, (W *)ovx);
     });
     GB_LAUNCH_CHECK();
     if (wcode != ct) {
@@ -531,13 +512,13 @@ void gb_writeback_matrix(GB_Obj *C, gb_mat_result &T, GB_Obj *M, const gb_desc &
         gb_with_type(ct, [&](auto z) {
             using CT = decltype(z);
             if (cnz)
-                hipLaunchKernelGGL((k_merge_place_c<CT>), dim3(wb_grid(cnz)), dim3(WB_BLOCK), 0, gb_stream(), nrows,
-                                   cnz, cv.rowptr, cv.colidx, (const CT *)cv.vals, cv.iso, T.rowptr, T.colidx, sc, st,
-                                   oci, (CT *)ovx);
+                hipLaunchKernelGGL((k_merge_place_c<CT>), dim3(gb_grid(cnz, WB_BLOCK, WB_GRID_CAP)), dim3(WB_BLOCK), 0,
+                                   gb_stream(), nrows, cnz, cv.rowptr, cv.colidx, (const CT *)cv.vals, cv.iso, T.rowptr,
+                                   T.colidx, sc, st, oci, (CT *)ovx);
             if (tnz && t_direct)
-                hipLaunchKernelGGL((k_merge_place_t<CT>), dim3(wb_grid(tnz)), dim3(WB_BLOCK), 0, gb_stream(), nrows,
-                                   tnz, T.rowptr, T.colidx, (const CT *)t_direct, T.iso, cv.rowptr, cv.colidx,
-                                   (const CT *)cv.vals, cv.iso, -2, sc, st, oci, (CT *)ovx);
+                hipLaunchKernelGGL((k_merge_place_t<CT>), dim3(gb_grid(tnz, WB_BLOCK, WB_GRID_CAP)), dim3(WB_BLOCK), 0,
+                                   gb_stream(), nrows, tnz, T.rowptr, T.colidx, (const CT *)t_direct, T.iso, cv.rowptr,
+                                   cv.colidx, (const CT *)cv.vals, cv.iso, -2, sc, st, oci, (CT *)ovx);
         });
         GB_LAUNCH_CHECK();
     }
