@@ -532,6 +532,9 @@ GrB_Info GxB_Global_get_int(const char *key, int64_t *value) {
     }
     // named kernel-class counters (gb_stat_add): "stat_" + name; 0 before the first count
     if (!strncmp(key, "stat_", 5)) {
+        // a vector eWiseUnion leaves its counts on the device until they are asked for
+        const GrB_Info info = gb_api(nullptr, [&] { gb_union_stat_refresh(key); });
+        if (info != GrB_SUCCESS) return info;
         if (!gb_stat_get(key + 5, value)) *value = 0;
         return GrB_SUCCESS;
     }

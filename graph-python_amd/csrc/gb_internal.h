@@ -596,6 +596,15 @@ void gb_select(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_IndexUnaryOp op, GB
 void gb_kronecker(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_BinaryOp binop, GB_Obj *A, GB_Obj *B,
                   const gb_desc &d);
 
+// eWiseUnion (gb_ewise_union.hip): T on A' union B' = add(a, b) / add(a, beta) / add(alpha, b), written
+// back as C<M> = C accum T.  alpha and beta point at host values already of add's input type
+// (GxB_{Matrix,Vector}_eWiseUnion in gb_scalar_args.cpp read and cast the GrB_Scalars)
+void gb_ewise_union(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_BinaryOp add, GB_Obj *A, const void *alpha,
+                    GB_Obj *B, const void *beta, const gb_desc &d);
+// GxB_Global_get_int asks here first: brings "stat_union_*" up to date after a vector call,
+// whose counts stay on the device until somebody reads them
+void gb_union_stat_refresh(const char *key);
+
 // sort (gb_sort.hip): the entry points are GxB_Matrix_sort / GxB_Vector_sort; GxB_Global_get_int
 // asks here for "stat_sort_rows_{wave,block,long}" (rows each class took in the last matrix sort,
 // read from the device) and for the defaults of "sort_wave_max" / "sort_block_max"

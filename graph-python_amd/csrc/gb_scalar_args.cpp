@@ -10,14 +10,18 @@
 //                                              core/matrix.py:2392,2435
 //   GrB_{Vector,Matrix}_select_Scalar          reference core/vector.py:1463-1560,
 //                                              core/matrix.py:2452-2551
+//   GxB_{Vector,Matrix}_eWiseUnion             reference core/vector.py:1141-1260,
+//                                              core/matrix.py:2044-2161
 // Each reads the scalar's value (its own type) on the host and forwards to the typed entry
 // point of that type, which casts it as the typed call would.  An empty GrB_Scalar means
 // "no value" (C API 2.0): setElement deletes the entry; extractElement of a missing entry
 // clears the scalar and succeeds; assign acts as the assignment of an empty object (the
-// selected part of the region is deleted, or left alone under accum); apply fails with
-// GrB_EMPTY_OBJECT.  Host work only (a one-element read); the hot path never calls these.
+// selected part of the region is deleted, or left alone under accum); apply, select and
+// eWiseUnion fail with GrB_EMPTY_OBJECT.  eWiseUnion casts its two defaults to the operator's
+// input type here and hands them to gb_ewise_union (gb_ewise_union.hip).  Host work only (a one-element read); the hot path never calls these.
 #include <cstring>
 
+#include "gb_dispatch.cuh"
 #include "gb_internal.h"
 
 namespace {
@@ -193,9 +197,47 @@ GrB_Info select_scalar(bool vec, OUT w, const OUT mask, const GrB_BinaryOp accum
     }
     return GrB_DOMAIN_MISMATCH;
 }
+
+// alpha and beta read on the host; op's input type is known only once op is checked, so the
+// cast happens inside the API wrapper (cast: the two values as that type, 8 bytes each)
+template <class OUT>
+GrB_Info ewise_union(OUT C, const OUT Mask, const GrB_BinaryOp accum, const GrB_BinaryOp add, const OUT A,
+                     const GrB_Scalar alpha, const OUT B, const GrB_Scalar beta, const GrB_Descriptor desc,
+                     const char *name) {
+    if (!C || !A || !B || !add || !alpha || !beta) return GrB_NULL_POINTER;
+    sval va, vb;
+    GrB_Info e = read_scalar(va, alpha);
+    if (e == GrB_SUCCESS) e = read_scalar(vb, beta);
+    if (e != GrB_SUCCESS) return e;
+    if (!va.present || !vb.present)
+        return fail_on(C, GrB_EMPTY_OBJECT, "eWiseUnion: a default GrB_Scalar holds no value");
+    return gb_api_impl(
+        OBJ(C),
+        [&] {
+            gb_check_binop(add, false);
+            GB_REQUIRE(add->xtype != nullptr, GrB_NOT_IMPLEMENTED, "positional eWiseUnion operator");
+            alignas(8) unsigned char ca[8] = {}, cb[8] = {};
+            gb_cast_scalar(ca, add->xtype->code, va.bytes, va.code);
+            gb_cast_scalar(cb, add->xtype->code, vb.bytes, vb.code);
+            gb_ewise_union(gb_obj_check(C), gb_obj_check(Mask, true), accum, add, gb_obj_check(A), ca, gb_obj_check(B),
+                           cb, gb_read_desc(desc));
+        },
+        name);
+}
 }  // namespace
 
 extern "C" {
+
+GrB_Info GxB_Matrix_eWiseUnion(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_BinaryOp add,
+                               const GrB_Matrix A, const GrB_Scalar alpha, const GrB_Matrix B, const GrB_Scalar beta,
+                               const GrB_Descriptor desc) {
+    return ewise_union(C, Mask, accum, add, A, alpha, B, beta, desc, __func__);
+}
+GrB_Info GxB_Vector_eWiseUnion(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, const GrB_BinaryOp add,
+                               const GrB_Vector u, const GrB_Scalar alpha, const GrB_Vector v, const GrB_Scalar beta,
+                               const GrB_Descriptor desc) {
+    return ewise_union(w, mask, accum, add, u, alpha, v, beta, desc, __func__);
+}
 
 GrB_Info GrB_Vector_setElement_Scalar(GrB_Vector w, const GrB_Scalar x, GrB_Index i) {
     sval v;

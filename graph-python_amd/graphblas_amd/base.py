@@ -428,6 +428,11 @@ class BaseType:
 
         return _ewise_infix_expr(self, other, "ewise_add")
 
+    def __sub__(self, other):
+        from .infix import _sub_infix_expr
+
+        return _sub_infix_expr(self, other)
+
     def __imatmul__(self, other):
         self << self @ other
         return self

@@ -1,5 +1,6 @@
 """`A @ B` delayed matmul expressions (reference core/infix.py:251-259, 388-397,
-444-497; default semiring resolution core/expr.py:504-508)."""
+444-497; default semiring resolution core/expr.py:504-508), `x | y` / `x & y`, and `x - y`
+(reference core/infixmethods.py:237-242)."""
 from . import operator as _op
 
 
@@ -71,3 +72,15 @@ def _ewise_infix_expr(left, right, method):
     if getattr(left, "ndim", None) is None or getattr(right, "ndim", None) is None:
         return NotImplemented
     return InfixExpr(left, right, method)
+
+
+def _sub_infix_expr(left, right):
+    """`A - B` / `v - w` between two collections of the same kind: ewise_union(binary.minus, 0, 0)
+    (reference core/infixmethods.py:237-242).  A scalar operand is not handled here."""
+    from .matrix import Matrix, TransposedMatrix
+    from .vector import Vector
+
+    mats = (Matrix, TransposedMatrix)
+    if (isinstance(left, mats) and isinstance(right, mats)) or (isinstance(left, Vector) and isinstance(right, Vector)):
+        return left.ewise_union(right, _op.binary.minus, 0, 0)
+    return NotImplemented

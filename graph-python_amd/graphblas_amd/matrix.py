@@ -313,6 +313,9 @@ class Matrix(BaseType):
     def ewise_add(self, other, op=None):
         return _ewise(self, other, op if op is not None else _op.monoid.plus, "add")
 
+    def ewise_union(self, other, op, left_default, right_default):
+        return _ewise_union(self, other, op, left_default, right_default)
+
     def reduce_scalar(self, op=None, *, allow_empty=True):
         return _reduce_scalar(self, op, allow_empty)
 
@@ -523,6 +526,9 @@ class TransposedMatrix:
     def ewise_add(self, other, op=None):
         return _ewise(self, other, op if op is not None else _op.monoid.plus, "add")
 
+    def ewise_union(self, other, op, left_default, right_default):
+        return _ewise_union(self, other, op, left_default, right_default)
+
     def power(self, n, op=None):
         return self.new().power(n, op)
 
@@ -561,6 +567,11 @@ class TransposedMatrix:
         from .infix import _matmul_infix_expr
 
         return _matmul_infix_expr(other, self)
+
+    def __sub__(self, other):
+        from .infix import _sub_infix_expr
+
+        return _sub_infix_expr(self, other)
 
 
 def _is_agg(op):
@@ -782,6 +793,55 @@ def _ewise(left, right, opobj, kind):
     cf = "GrB_Matrix_eWiseMult_BinaryOp" if kind == "mult" else "GrB_Matrix_eWiseAdd_BinaryOp"
     return MatrixExpression(f"ewise_{kind}", cf, [a, b], op=op, at=at, bt=bt, nrows=left.nrows,
                             ncols=left.ncols)
+
+
+def _union_default(value, keyword):
+    """A default of ewise_union as a Scalar: a Scalar as it is, a literal through Scalar.from_value."""
+    from .scalar import Scalar
+
+    if isinstance(value, Scalar):
+        return value
+    try:
+        a = np.asarray(value)
+        if a.ndim != 0 or a.dtype == object:
+            raise TypeError("not a scalar")
+        dtype = lookup_dtype(a.dtype)
+    except (TypeError, ValueError) as exc:
+        raise TypeError(f"Bad type for keyword argument `{keyword}` in ewise_union: expected Scalar, got "
+                        f"{type(value).__name__}.  Literal scalars also accepted.") from exc
+    return Scalar.from_value(a.item(), dtype)
+
+
+def _ewise_union(left, right, op, left_default, right_default):
+    """x.ewise_union(y, op, left_default, right_default) (reference core/matrix.py:2044-2161,
+    core/vector.py:1141-1260) -> GxB_{Matrix,Vector}_eWiseUnion: op(x, y) where both are stored,
+    op(x, right_default) where only x is, op(left_default, y) where only y is.  The operator is
+    typed from the defaults unified with the operands, so float defaults upcast integer operands."""
+    from .vector import Vector, VectorExpression
+
+    kind = "Vector" if left.ndim == 1 else "Matrix"
+    want = (Vector,) if kind == "Vector" else (Matrix, TransposedMatrix)
+    if not isinstance(right, want):
+        raise TypeError(f"Bad type for argument `other` in ewise_union: expected {kind}, got "
+                        f"{type(right).__name__}")
+    ld = _union_default(left_default, "left_default")
+    rd = _union_default(right_default, "right_default")
+    t = _op.get_typed_op(op, unify(ld.dtype, rd.dtype), unify(left.dtype, right.dtype), kind="binary",
+                         is_left_scalar=True)
+    if t.opclass == "Monoid":
+        t = getattr(_op.binary, t.parent.name if t.parent.name != "eq" else "lxnor")[t.type]
+    elif t.opclass != "BinaryOp":
+        raise TypeError(f"Bad type for argument `op` in ewise_union: expected BinaryOp or Monoid, got {t.opclass}")
+    if t.is_positional:
+        raise NotImplementedError("positional operators in ewise_union")
+    if left.shape != right.shape:
+        raise DimensionMismatch(f"Dimensions do not match: {left.shape} and {right.shape}")
+    if kind == "Vector":
+        return VectorExpression("ewise_union", "GxB_Vector_eWiseUnion", [left, ld, right, rd], op=t, size=left.size)
+    a, at = _unwrap(left)
+    b, bt = _unwrap(right)
+    return MatrixExpression("ewise_union", "GxB_Matrix_eWiseUnion", [a, ld, b, rd], op=t, at=at, bt=bt,
+                            nrows=left.nrows, ncols=left.ncols)
 
 
 def _kronecker(left, right, op):

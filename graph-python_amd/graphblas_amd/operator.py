@@ -46,8 +46,8 @@ class TypedOp:
     def __repr__(self):
         return f"{self.opclass.lower()}.{self.name}[{self.type}]"
 
-    def __call__(self, expr, right=None):
-        return _call_op(self, expr, right)
+    def __call__(self, expr, right=None, *, left_default=None, right_default=None):
+        return _call_op(self, expr, right, left_default, right_default)
 
 
 class OpBase:
@@ -79,8 +79,8 @@ class OpBase:
     def __repr__(self):
         return f"{self.opclass.lower()}.{self.name}"
 
-    def __call__(self, expr, right=None):
-        return _call_op(self, expr, right)
+    def __call__(self, expr, right=None, *, left_default=None, right_default=None):
+        return _call_op(self, expr, right, left_default, right_default)
 
 
 class BinaryOp(OpBase):
@@ -388,11 +388,21 @@ def find_opclass(obj):
     return obj, "Unknown"
 
 
-def _call_op(opobj, expr, right=None):
+def _call_op(opobj, expr, right=None, left_default=None, right_default=None):
     """semiring(A @ B) / binary.plus(x | y) / binary.plus(x, 1) / unary.abs(x) style
-    (reference core/operator/base.py:110-161, binary.py:175-230)."""
+    (reference core/operator/base.py:110-161, binary.py:175-230); binary.minus(x | y,
+    left_default=0, right_default=0) is x.ewise_union(y, ...) (reference binary.py:81-97)."""
     from .infix import InfixExpr
 
+    if left_default is not None or right_default is not None:
+        if (left_default is None or right_default is None or right is not None
+                or not isinstance(expr, InfixExpr) or expr.method != "ewise_add"):
+            raise TypeError("Specifying `left_default` or `right_default` keyword arguments implies "
+                            "performing `ewise_union` operation with infix notation.\n"
+                            "There is only one valid way to do this:\n\n"
+                            f">>> {opobj}(x | y, left_default=0, right_default=0)\n\nwhere x and y "
+                            "are Vectors or Matrices, and left_default and right_default are scalars.")
+        return expr.left.ewise_union(expr.right, opobj, left_default, right_default)
     if isinstance(expr, InfixExpr):
         return expr._with_op(opobj)
     if right is not None:

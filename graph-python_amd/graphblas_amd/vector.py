@@ -261,6 +261,11 @@ class Vector(BaseType):
     def ewise_add(self, other, op=None):
         return self._ewise(other, op if op is not None else _op.monoid.plus, "add")
 
+    def ewise_union(self, other, op, left_default, right_default):
+        from .matrix import _ewise_union
+
+        return _ewise_union(self, other, op, left_default, right_default)
+
     def _ewise(self, other, opobj, kind):
         op = _op.get_typed_op(opobj, self.dtype, other.dtype, kind="binary")
         if op.opclass == "Monoid":

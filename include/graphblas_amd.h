@@ -343,6 +343,17 @@ GrB_Info GrB_Matrix_kronecker_Semiring(GrB_Matrix C, const GrB_Matrix Mask, cons
  * w(k) is the rank-k value of u and p(k) its original index, k < nvals(u). */
 GrB_Info GxB_Matrix_sort(GrB_Matrix C, GrB_Matrix P, GrB_BinaryOp op, const GrB_Matrix A, const GrB_Descriptor desc);
 GrB_Info GxB_Vector_sort(GrB_Vector w, GrB_Vector p, GrB_BinaryOp op, const GrB_Vector u, const GrB_Descriptor desc);
+/* eWiseUnion (reference core/matrix.py:2044-2161, core/vector.py:1141-1260): C<M> = accum(C, T),
+ * T on the structure of A' union B' (after GrB_INP0 / GrB_INP1) with the type of add's result:
+ * add(A'(i,j), B'(i,j)) where both are stored, add(A'(i,j), beta) where only A' is and
+ * add(alpha, B'(i,j)) where only B' is.  A', B', alpha and beta are cast to add's input type.
+ * An empty alpha or beta is GrB_EMPTY_OBJECT, a positional add GrB_NOT_IMPLEMENTED. */
+GrB_Info GxB_Matrix_eWiseUnion(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum,
+                               const GrB_BinaryOp add, const GrB_Matrix A, const GrB_Scalar alpha,
+                               const GrB_Matrix B, const GrB_Scalar beta, const GrB_Descriptor desc);
+GrB_Info GxB_Vector_eWiseUnion(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum,
+                               const GrB_BinaryOp add, const GrB_Vector u, const GrB_Scalar alpha,
+                               const GrB_Vector v, const GrB_Scalar beta, const GrB_Descriptor desc);
 
 /* ---------------------------------------------------------------- the hot path */
 /* C<Mask> = C accum (A' (+).(x) B')      replaces SuiteSparse GrB_mxm */
@@ -528,7 +539,8 @@ GrB_Info GxB_MatrixMarket_free(void *p);
  * the longest row of the sub-wave and of the workgroup class, which can only be lowered and
  * read back as their defaults while unset).  get_int also reads "stat_sort_rows_wave" /
  * "stat_sort_rows_block" / "stat_sort_rows_long" (rows each class took in the last sort),
- * the read-only counters "stat_bfs_spec_adopted" / "stat_bfs_spec_rollbacks" (BFS level
+ * "stat_union_both" / "stat_union_a_only" / "stat_union_b_only" (entries of T the last
+ * eWiseUnion computed from both operands, from A' and beta, from alpha and B'), the read-only counters "stat_bfs_spec_adopted" / "stat_bfs_spec_rollbacks" (BFS level
  * speculation) and "stat_nvals_copy" (vector counts read by a device copy
  * instead of the producing kernel's host mailbox). */
 GrB_Info GxB_Global_set_int(const char *key, int64_t value);
