@@ -84,10 +84,15 @@ struct gb_orient_cache {
     // hub-chunk table, built by gb_view_hubs (gb_mxv.hip)
     int32_t *hub_tab = nullptr;
     int64_t hub_n = 0, hub_H = 0;
-    // bitmap of the non-empty rows
+    // bitmap of the non-empty rows, and its per-word exclusive prefix (gb_view_nonempty,
+    // gb_mxv.hip): ne_rank[w] = non-empty rows in the words before w, words + 1 entries (the
+    // last one their count; row ids are int32, so 32 bits hold it).  Row r's rank among the
+    // non-empty rows is ne_rank[r >> 6] + popcount(rows_ne[r >> 6] & bits below r & 63)
     uint64_t *rows_ne = nullptr;
-    // pull heads (gb_view_pullfirst, gb_mxv.hip):
-    // per row 4 int32 -- its neighbours with the most entries in the other orientation
+    uint32_t *ne_rank = nullptr;
+    // pull heads (gb_view_pullfirst, gb_mxv.hip), one record per non-empty row, indexed by
+    // that rank (an empty row is never open in the pull and has no record):
+    // 4 int32 -- the row's neighbours with the most entries in the other orientation
     // first, the whole row when it has at most 4 (padding -1), else 3 of them and -2 -- and
     // the row's own length in the other orientation (saturated to 32 bits)
     int32_t *phead = nullptr;
@@ -375,8 +380,9 @@ struct gb_csr_view {
     const int32_t *hubs = nullptr;
     int64_t nhubs = 0, hub_H = 0;
     const uint64_t *nonempty = nullptr;  // bitmap of rows with entries (when attached)
-    const int32_t *phead = nullptr;      // pull head per row, 4 int32 (when attached; see gb_orient_cache)
-    const uint32_t *pdeg = nullptr;      // row length in the other orientation (when attached)
+    const uint32_t *ne_rank = nullptr;   // its per-word exclusive prefix, words + 1 entries (attached with it)
+    const int32_t *phead = nullptr;      // pull head per non-empty row by rank, 4 int32 (when attached; see gb_orient_cache)
+    const uint32_t *pdeg = nullptr;      // row length in the other orientation, by rank (when attached)
     int64_t maxdeg = -1;                 // longest row (host; attached with the hub chunks, -1 unknown)
     const int32_t *lchunks = nullptr;    // long-row chunks (row, piece) of the general SpMV (when attached)
     int64_t nlchunks = -1;
@@ -390,11 +396,13 @@ struct gb_csr_view {
 void gb_get_csr(gb_csr_view &v, GB_Obj *A);
 // attach the cached hub-chunk table of matrix A's orientation (0 CSR, 1 CSC) to v
 void gb_view_hubs(gb_csr_view &v, GB_Obj *A, int orient, int64_t H);
-// attach the cached non-empty-rows bitmap of matrix A's orientation to v
+// attach the cached non-empty-rows bitmap of matrix A's orientation, and its rank prefix, to v
 void gb_view_nonempty(gb_csr_view &v, GB_Obj *A, int orient);
 // attach the cached pull heads of A's orientation (other_rowptr: the other orientation's row
 // pointers, other_n rows) -- the iso pull tests a row's best-connected neighbours first, and
-// rows of at most 4 entries without reading their bounds or edges
+// rows of at most 4 entries without reading their bounds or edges.  The heads are indexed by
+// rank among the non-empty rows: v must carry gb_view_nonempty's bitmap and prefix, and gets
+// no heads otherwise
 void gb_view_pullfirst(gb_csr_view &v, GB_Obj *A, int orient, const int64_t *other_rowptr, int64_t other_n);
 void gb_view_long_rows(gb_csr_view &v, GB_Obj *A, int orient);
 // attach the cached narrow copy of matrix A's orientation's integer values (built on first use:

@@ -592,28 +592,53 @@ void gb_view_long_rows(gb_csr_view &v, GB_Obj *A, int orient) {
     v.nlchunks = c.long_n;
 }
 
-__global__ void k_rows_nonempty(const int64_t *__restrict__ rowptr, int64_t n, uint64_t *__restrict__ ne) {
+// ne[w]: bitmap word of the rows with entries (bits past n clear); pc[w]: its popcount
+__global__ void k_rows_nonempty(const int64_t *__restrict__ rowptr, int64_t n, uint64_t *__restrict__ ne,
+                                int32_t *__restrict__ pc) {
     const int lane = threadIdx.x & 63;
     const int64_t nw = (n + 63) >> 6;
     for (int64_t w = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6; w < nw;
          w += ((int64_t)gridDim.x * blockDim.x) >> 6) {
         const int64_t r = (w << 6) + lane;
         const unsigned long long b = __ballot(r < n && rowptr[r + 1] > rowptr[r]);
-        if (lane == 0) ne[w] = b;
+        if (lane == 0) {
+            ne[w] = b;
+            pc[w] = __popcll(b);
+        }
     }
 }
 
+__global__ void k_narrow_u32(const int64_t *__restrict__ in, uint32_t *__restrict__ out, int64_t n) {
+    GB_GRID_LOOP(i, n)
+        out[i] = (uint32_t)in[i];
+}
+
+// the bitmap and, with it, its per-word exclusive prefix ne_rank (words + 1 entries, the last
+// one the count of non-empty rows): the words' popcounts through the scan of gb_prim.hip
 void gb_view_nonempty(gb_csr_view &v, GB_Obj *A, int orient) {
     if (A->kind != GB_KIND_MATRIX) return;
     gb_orient_cache &c = A->oc[orient];
     if (!c.rows_ne) {
         const int64_t nw = gb_words(v.nrows);
         c.rows_ne = gb_malloc_n<uint64_t>(nw);
-        const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nw + 3) / 4, 8192));
-        hipLaunchKernelGGL(k_rows_nonempty, dim3(g), dim3(256), 0, gb_stream(), v.rowptr, v.nrows, c.rows_ne);
-        GB_LAUNCH_CHECK();
+        c.ne_rank = gb_malloc_n<uint32_t>(nw + 1);
+        if (nw == 0) {
+            gb_memset(c.ne_rank, 0, sizeof(uint32_t));
+        } else {
+            gb_scratch s;
+            int32_t *pc = s.get<int32_t>(nw);
+            int64_t *pre = s.get<int64_t>(nw + 1);
+            const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nw + 3) / 4, 8192));
+            hipLaunchKernelGGL(k_rows_nonempty, dim3(g), dim3(256), 0, gb_stream(), v.rowptr, v.nrows, c.rows_ne, pc);
+            GB_LAUNCH_CHECK();
+            gb_exclusive_scan_i32(pc, 0, pre, nw);
+            hipLaunchKernelGGL(k_narrow_u32, dim3(gb_grid(nw + 1, 256, 4096)), dim3(256), 0, gb_stream(), pre,
+                               c.ne_rank, nw + 1);
+            GB_LAUNCH_CHECK();
+        }
     }
     v.nonempty = c.rows_ne;
+    v.ne_rank = c.ne_rank;
 }
 
 // pull heads: a wave per row picks its neighbours with the longest rows in the other
@@ -628,14 +653,19 @@ __device__ __forceinline__ void pf_better(int64_t &bd, int32_t &bi, int64_t d, i
         bi = i;
     }
 }
+// The records are indexed by the row's rank among the non-empty rows (ne: their bitmap, rank:
+// its per-word exclusive prefix, gb_view_nonempty); a row without entries has none.
 __global__ __launch_bounds__(256) void k_pull_head(int64_t n, const int64_t *__restrict__ rp,
                                                    const int32_t *__restrict__ ci,
                                                    const int64_t *__restrict__ orp, int64_t on,
+                                                   const uint64_t *__restrict__ ne, const uint32_t *__restrict__ rank,
                                                    int4 *__restrict__ head, uint32_t *__restrict__ pdeg) {
     const int lane = threadIdx.x & 63;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     for (int64_t j = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6; j < n; j += nwaves) {
         const int64_t e0 = rp[j], e1 = rp[j + 1], d = e1 - e0;
+        if (d <= 0) continue;  // the wave's row is empty: no record
+        const int64_t slot = (int64_t)rank[j >> 6] + __popcll(ne[j >> 6] & ((1ULL << (j & 63)) - 1));
         int32_t pick[4] = {-1, -1, -1, -1};
         const int rounds = d <= 4 ? (int)d : 3;
         for (int r = 0; r < rounds; r++) {
@@ -656,10 +686,10 @@ __global__ __launch_bounds__(256) void k_pull_head(int64_t n, const int64_t *__r
         }
         if (d > 4) pick[3] = -2;
         if (lane == 0) {
-            head[j] = make_int4(pick[0], pick[1], pick[2], pick[3]);
+            head[slot] = make_int4(pick[0], pick[1], pick[2], pick[3]);
             if (pdeg) {
                 const int64_t od = j < on ? orp[j + 1] - orp[j] : 0;
-                pdeg[j] = (uint32_t)(od < 0xFFFFFFFFLL ? od : 0xFFFFFFFFLL);
+                pdeg[slot] = (uint32_t)(od < 0xFFFFFFFFLL ? od : 0xFFFFFFFFLL);
             }
         }
     }
@@ -668,12 +698,19 @@ __global__ __launch_bounds__(256) void k_pull_head(int64_t n, const int64_t *__r
 void gb_view_pullfirst(gb_csr_view &v, GB_Obj *A, int orient, const int64_t *other_rowptr, int64_t other_n) {
     if (A->kind != GB_KIND_MATRIX || v.nrows == 0) return;
     gb_orient_cache &c = A->oc[orient];
+    // the records are found through the non-empty bitmap's ranks: no heads without them
+    if (!c.rows_ne || !c.ne_rank || v.nonempty != c.rows_ne || v.ne_rank != c.ne_rank) return;
     if (!c.phead) {
-        c.phead = gb_malloc_n<int32_t>(4 * v.nrows);
-        c.pdeg = gb_malloc_n<uint32_t>(v.nrows);
+        // one record per non-empty row: their count is the prefix's last entry (read once per
+        // matrix orientation, when the heads are built)
+        uint32_t ne_count = 0;
+        gb_copy_d2h(&ne_count, c.ne_rank + gb_words(v.nrows), sizeof(ne_count));
+        const int64_t nrec = std::max<int64_t>(1, (int64_t)ne_count);
+        c.phead = gb_malloc_n<int32_t>(4 * nrec);
+        c.pdeg = gb_malloc_n<uint32_t>(nrec);
         const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((v.nrows + 3) / 4, 65535));
         hipLaunchKernelGGL(k_pull_head, dim3(g), dim3(256), 0, gb_stream(), v.nrows, v.rowptr, v.colidx,
-                           other_rowptr, other_n, reinterpret_cast<int4 *>(c.phead), c.pdeg);
+                           other_rowptr, other_n, c.rows_ne, c.ne_rank, reinterpret_cast<int4 *>(c.phead), c.pdeg);
         GB_LAUNCH_CHECK();
     }
     v.phead = c.phead;

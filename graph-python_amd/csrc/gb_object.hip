@@ -105,6 +105,7 @@ void gb_drop_transpose(GB_Obj *A) {
 void gb_orient_cache_drop(gb_orient_cache &c) {
     gb_free(c.hub_tab);
     gb_free(c.rows_ne);
+    gb_free(c.ne_rank);
     gb_free(c.phead);
     gb_free(c.pdeg);
     gb_free(c.long_tab);

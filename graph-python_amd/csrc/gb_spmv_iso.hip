@@ -444,6 +444,19 @@ __device__ __forceinline__ long long gb_push_root(int64_t root, const int64_t *_
     return added;
 }
 
+// The pull heads and pdeg hold one record per non-empty row, indexed by the row's rank among
+// them: the prefix of the row's bitmap word (ne_rank, loaded with the step's other control
+// words) + the non-empty rows below it in the word (rw: the word of rows_nonempty).
+__device__ __forceinline__ uint32_t gb_ne_rank(uint32_t prefix, uint64_t rw, int bit) {
+    return prefix + (uint32_t)__popcll(rw & ((1ULL << bit) - 1));
+}
+// lane l's 64-bit x on every lane (l wave-uniform)
+__device__ __forceinline__ uint64_t gb_readlane64(uint64_t x, int l) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), l);
+    return ((uint64_t)hi << 32) | lo;
+}
+
 // The pull-head probes of a wave step in two rounds, each with every load in flight at once:
 // the first head of every open row, then the other three for the rows it missed (a
 // short-circuit test makes each probe wait for the one before it: up to 16 dependent
@@ -529,7 +542,8 @@ __device__ __forceinline__ long long gb_pull_iso_phase(int64_t nrows, const int6
                                                       const uint64_t *__restrict__ qbits, const gb_asg_dev &g,
                                                       long long &adelta, int dbg = 0,
                                                       const int32_t *__restrict__ ph = nullptr,
-                                                      const uint32_t *__restrict__ pdeg = nullptr) {
+                                                      const uint32_t *__restrict__ pdeg = nullptr,
+                                                      const uint32_t *__restrict__ nrk = nullptr) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -545,6 +559,7 @@ __device__ __forceinline__ long long gb_pull_iso_phase(int64_t nrows, const int6
         const uint64_t qw = (qbits && inr) ? qbits[wl] : 0;
         const uint64_t mw = (mbits && inr) ? mbits[wl] : 0;
         const uint64_t rw = (rne && inr) ? rne[wl] : ~0ULL;
+        const uint32_t nr = (ph && inr) ? nrk[wl] : 0;  // the heads' rank prefix: the same round trip
         uint64_t mine = ~0ULL;
         if (qbits) {  // fused assign: w |= q; the mask is w's structure after it
             adelta += gb_asg_words(g, w0, nwords, qw, lane, g.bits == mbits ? &mw : nullptr);
@@ -573,10 +588,12 @@ __device__ __forceinline__ long long gb_pull_iso_phase(int64_t nrows, const int6
             // their bounds or edges -- the dependent row-pointer / edge round trips are left to
             // the long rows that found nothing
             int4 hv[PULL_U];
+            uint32_t rk[PULL_U];  // the rows' records (an open row has entries: its bit is set in rw)
 #pragma unroll
             for (int u = 0; u < PULL_U; u++) {
+                rk[u] = gb_ne_rank((uint32_t)__builtin_amdgcn_readlane((int)nr, u), gb_readlane64(rw, u), lane);
                 hv[u] = make_int4(-1, -1, -1, -1);
-                if (live[u]) hv[u] = reinterpret_cast<const int4 *>(ph)[((w0 + u) << 6) + lane];
+                if (live[u]) hv[u] = reinterpret_cast<const int4 *>(ph)[rk[u]];
             }
             if (dbg & 128) {  // diagnostics: the round-4 short-circuit probes (A/B)
 #pragma unroll
@@ -596,7 +613,7 @@ __device__ __forceinline__ long long gb_pull_iso_phase(int64_t nrows, const int6
                     p[u] = rowptr[r];
                     p1[u] = rowptr[r + 1];
                 }
-                dg[u] = (hprow && found[u]) ? (int64_t)pdeg[r] : p1[u] - p[u];
+                dg[u] = (hprow && found[u]) ? (int64_t)pdeg[rk[u]] : p1[u] - p[u];
             }
         } else {
             // row bounds are loaded for every row, independently of the mask word
@@ -698,6 +715,8 @@ __device__ __forceinline__ long long gb_pull_iso_phase(int64_t nrows, const int6
 struct gb_wpack {
     int16_t ids[PACK_W * 64];           // the group's open rows in order: word in group * 64 + bit
     unsigned long long fw[PACK_W];      // found flags of the packed slots, 64 per word
+    unsigned long long rw[PACK_W];      // the group's words of rows_nonempty, by owning lane, and
+    uint32_t rk[PACK_W];                // their rank prefixes: a packed row's record is gb_ne_rank of the pair
 };
 __device__ __forceinline__ long long gb_pull_iso_packed(int64_t nrows, const int64_t *__restrict__ rowptr,
                                                        const int32_t *__restrict__ colidx,
@@ -708,7 +727,8 @@ __device__ __forceinline__ long long gb_pull_iso_packed(int64_t nrows, const int
                                                        const uint64_t *__restrict__ rne,
                                                        const uint64_t *__restrict__ qbits, const gb_asg_dev &g,
                                                        long long &adelta, const int32_t *__restrict__ ph,
-                                                       const uint32_t *__restrict__ pdeg) {
+                                                       const uint32_t *__restrict__ pdeg,
+                                                       const uint32_t *__restrict__ nrk) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -724,6 +744,7 @@ __device__ __forceinline__ long long gb_pull_iso_packed(int64_t nrows, const int
         const uint64_t qw = (qbits && inr) ? qbits[wl] : 0;
         const uint64_t mw = (mbits && inr) ? mbits[wl] : 0;
         const uint64_t rw = (rne && inr) ? rne[wl] : ~0ULL;
+        const uint32_t nr = inr ? nrk[wl] : 0;  // the heads' rank prefix: the same round trip
         uint64_t mine = ~0ULL;
         if (qbits) {  // fused assign (gb_asg_words): w |= q, w's value at each q bit = x
             if (qw) {
@@ -765,10 +786,15 @@ __device__ __forceinline__ long long gb_pull_iso_packed(int64_t nrows, const int
             const int base = __shfl(excl, u, 64);
             if ((word >> lane) & 1ULL) P.ids[base + __popcll(word & lt)] = (int16_t)(u * 64 + lane);
         }
+        if (lane < PACK_W) {  // the batch lanes know a row by its owner lane and bit only
+            P.rw[lane] = rw;
+            P.rk[lane] = nr;
+        }
         gb_wave_sync();
         for (int b0 = 0; b0 < total; b0 += 256) {
             bool live[PULL_U], found[PULL_U];
             int64_t r[PULL_U];
+            uint32_t rk[PULL_U];
             int4 hv[PULL_U];
 #pragma unroll
             for (int u = 0; u < PULL_U; u++) {
@@ -776,8 +802,9 @@ __device__ __forceinline__ long long gb_pull_iso_packed(int64_t nrows, const int
                 live[u] = i < total;
                 const int id = live[u] ? P.ids[i] : 0;
                 r[u] = ((wb + (int64_t)(id >> 8) * stride + ((id >> 6) & (PULL_U - 1))) << 6) + (id & 63);
+                rk[u] = gb_ne_rank(P.rk[id >> 6], P.rw[id >> 6], id & 63);
                 hv[u] = make_int4(-1, -1, -1, -1);
-                if (live[u]) hv[u] = reinterpret_cast<const int4 *>(ph)[r[u]];
+                if (live[u]) hv[u] = reinterpret_cast<const int4 *>(ph)[rk[u]];
             }
             gb_pull_probe_heads(hv, ubits, found);
             int64_t p[PULL_U], p1[PULL_U], dg[PULL_U];
@@ -788,7 +815,7 @@ __device__ __forceinline__ long long gb_pull_iso_packed(int64_t nrows, const int
                     p[u] = rowptr[r[u]];
                     p1[u] = rowptr[r[u] + 1];
                 }
-                dg[u] = (hprow && found[u]) ? (int64_t)pdeg[r[u]] : p1[u] - p[u];
+                dg[u] = (hprow && found[u]) ? (int64_t)pdeg[rk[u]] : p1[u] - p[u];
             }
             // rows still open -> segment list (ids local to the batch: u * 64 + lane)
             int n = 0;
@@ -901,8 +928,9 @@ struct gb_iso_args {
     int pack;                       // open rows packed across a wave's steps (knob iso_pack): 1 pull, 2 push
     bool packed;                    // one-round finish (iso_finish_packed): n < 2^27
     const uint64_t *rows_nonempty;  // pull rows with entries (nullptr: all)
-    const int32_t *phead;           // pull head per row, 4 int32 (nullptr: none; gb_view_pullfirst)
-    const uint32_t *pdeg;           // push-orientation length per pull row (the hint of found rows)
+    const uint32_t *ne_rank;        // its per-word exclusive prefix (gb_view_nonempty; the heads' index)
+    const int32_t *phead;           // pull head per non-empty row by rank, 4 int32 (nullptr: none; gb_view_pullfirst)
+    const uint32_t *pdeg;           // push-orientation length per non-empty pull row (the hint of found rows)
     int host_dir;                   // 1: push, decided on the host (small frontier of known size)
     // storage of cleared vectors zeroed by this launch (gb_zpool_*): bitmaps of zb_words words,
     // counts of 2 + GB_HINT_PARTS words
@@ -1085,13 +1113,15 @@ __global__ __launch_bounds__(SPMV_BLOCK) void k_iso_work(
                             (unsigned long long *)tbits, L, a.hprow, mfn, qbits, a.asg, adelta, (a.dbg & 128) != 0,
                             (a.dbg & 512) == 0, (a.pack & 2) != 0);
     else {
-        const int32_t *ph = (a.phead && (!a.hprow || a.pdeg)) ? a.phead : nullptr;
+        // the heads are found through the non-empty bitmap's ranks: without it, no heads
+        const int32_t *ph =
+            (a.phead && a.rows_nonempty && a.ne_rank && (!a.hprow || a.pdeg)) ? a.phead : nullptr;
         if ((a.pack & 1) && ph && a.p1_steps == 0 && !(a.dbg & (16 | 32 | 128)))
             cnt = gb_pull_iso_packed(nrows, rowptr, colidx, ubits, mbits, mcomp, tbits, L, packs[threadIdx.x >> 6],
-                                     a.hprow, mfn, a.cap0, a.rows_nonempty, qbits, a.asg, adelta, ph, a.pdeg);
+                                     a.hprow, mfn, a.cap0, a.rows_nonempty, qbits, a.asg, adelta, ph, a.pdeg, a.ne_rank);
         else
             cnt = gb_pull_iso_phase(nrows, rowptr, colidx, ubits, mbits, mcomp, tbits, L, a.hprow, mfn, a.p1_steps,
-                                    a.cap0, a.rows_nonempty, qbits, a.asg, adelta, a.dbg, ph, a.pdeg);
+                                    a.cap0, a.rows_nonempty, qbits, a.asg, adelta, a.dbg, ph, a.pdeg, a.ne_rank);
     }
     if (a.dbg & 64) return;  // diagnostics: no finish (count, hint, mailbox)
     if (a.packed) {
@@ -1249,6 +1279,7 @@ void gb_spmv_iso(gb_vec_result &T, const gb_csr_view &A, const gb_csr_view *Apus
     args.cap0 = (int)gb_knob("pull_cap");
     if (args.cap0 <= 0) args.cap0 = 64;
     args.rows_nonempty = A.nonempty;
+    args.ne_rank = A.ne_rank;
     args.phead = A.phead;
     args.pdeg = A.pdeg;
     // the result's iso value: evaluated by k_iso_work (gb_iso_eval), its only writer
