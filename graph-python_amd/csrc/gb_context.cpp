@@ -257,6 +257,10 @@ void gb_stat_add(const char *name, int64_t v) {
     std::lock_guard<std::mutex> lk(g_named_stat_mu);
     g_named_stats[name] += v;
 }
+void gb_stat_set(const char *name, int64_t v) {
+    std::lock_guard<std::mutex> lk(g_named_stat_mu);
+    g_named_stats[name] = v;
+}
 bool gb_stat_get(const char *name, int64_t *v) {
     std::lock_guard<std::mutex> lk(g_named_stat_mu);
     auto it = g_named_stats.find(name);

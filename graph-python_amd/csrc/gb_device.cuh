@@ -621,6 +621,39 @@ GB_DEV void gb_count_bounds(int rel, int first, int nb, int lane, int (&below)[W
     }
 }
 
+// The rows of the chunk of WPI * 64 entries that starts at p0 (row[u]: of entry
+// p0 + u * 64 + lane; meaningless at or beyond nvals).  next: where the row search of the wave's
+// previous chunk ended (-1: nowhere yet), a lower bound of where this one starts.  The row of
+// entry p is upper_bound(rowptr, p) - 1, which skips runs of empty rows; the chunk's row
+// boundaries sit one per lane when there are fewer than 64, else every lane searches its own.
+template <int WPI>
+GB_DEV void gb_chunk_rows(const int64_t *__restrict__ rowptr, int64_t nrows, int64_t nvals, int64_t p0, int lane,
+                           int64_t &next, int64_t (&row)[WPI]) {
+#pragma unroll
+    for (int u = 0; u < WPI; u++) row[u] = 0;
+    if (p0 >= nvals) return;
+    const int64_t plast = min(p0 + WPI * 64, nvals) - 1;
+    int64_t mine;
+    const int64_t rlo =
+        next < 0 ? gb_upper_bound(rowptr, 1, nrows, p0) : gb_wave_upper(rowptr, next, nrows, p0, lane, &mine);
+    const int64_t rhi = gb_wave_upper(rowptr, rlo, nrows, plast, lane, &mine);
+    next = rhi;
+    if (rhi - rlo < 64) {
+        const int nb = (int)(rhi - rlo);
+        const int rel = lane < nb ? (int)(mine - p0) : INT32_MAX;  // in [1, WPI * 64)
+        int below[WPI];
+        gb_count_bounds<WPI>(rel, 0, nb, lane, below);
+#pragma unroll
+        for (int u = 0; u < WPI; u++) row[u] = rlo + below[u] - 1;
+    } else {
+#pragma unroll
+        for (int u = 0; u < WPI; u++) {
+            const int64_t p = p0 + u * 64 + lane;
+            if (p < nvals) row[u] = gb_upper_bound(rowptr, rlo, rhi, p) - 1;
+        }
+    }
+}
+
 // (bool) of one value of runtime type `code` (mask semantics: -0.0 is false, NaN true)
 GB_DEV bool gb_dyn_nonzero(const void *p, int code) {
     switch (code) {

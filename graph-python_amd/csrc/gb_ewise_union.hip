@@ -34,38 +34,6 @@
 
 namespace {
 
-// The rows of the chunk of UNI_WPI * 64 entries that starts at p0 (row[u]: of entry
-// p0 + u * 64 + lane; meaningless at or beyond nvals).  next: where the row search of the wave's
-// previous chunk ended (-1: nowhere yet), a lower bound of where this one starts.  The row of
-// entry p is upper_bound(rowptr, p) - 1, which skips runs of empty rows; the chunk's row
-// boundaries sit one per lane when there are fewer than 64, else every lane searches its own.
-GB_DEV void uni_chunk_rows(const int64_t *__restrict__ rowptr, int64_t nrows, int64_t nvals, int64_t p0, int lane,
-                           int64_t &next, int64_t (&row)[UNI_WPI]) {
-#pragma unroll
-    for (int u = 0; u < UNI_WPI; u++) row[u] = 0;
-    if (p0 >= nvals) return;
-    const int64_t plast = min(p0 + UNI_WPI * 64, nvals) - 1;
-    int64_t mine;
-    const int64_t rlo =
-        next < 0 ? gb_upper_bound(rowptr, 1, nrows, p0) : gb_wave_upper(rowptr, next, nrows, p0, lane, &mine);
-    const int64_t rhi = gb_wave_upper(rowptr, rlo, nrows, plast, lane, &mine);
-    next = rhi;
-    if (rhi - rlo < 64) {
-        const int nb = (int)(rhi - rlo);
-        const int rel = lane < nb ? (int)(mine - p0) : INT32_MAX;  // in [1, UNI_WPI * 64)
-        int below[UNI_WPI];
-        gb_count_bounds<UNI_WPI>(rel, 0, nb, lane, below);
-#pragma unroll
-        for (int u = 0; u < UNI_WPI; u++) row[u] = rlo + below[u] - 1;
-    } else {
-#pragma unroll
-        for (int u = 0; u < UNI_WPI; u++) {
-            const int64_t p = p0 + u * 64 + lane;
-            if (p < nvals) row[u] = gb_upper_bound(rowptr, rlo, rhi, p) - 1;
-        }
-    }
-}
-
 // S(q): the B-only entries before entry q of B' (q <= nnz B': that word exists)
 GB_DEV int64_t uni_before(const uint64_t *__restrict__ words, const int64_t *__restrict__ base, int64_t q) {
     const int64_t w = q >> 6;
@@ -92,7 +60,7 @@ __global__ __launch_bounds__(UNI_BLOCK) void k_union_mark(int64_t nrows, int64_t
         const int64_t w0 = g * UNI_WPI;
         const int64_t p0 = w0 << 6;
         int64_t row[UNI_WPI];
-        uni_chunk_rows(brp, nrows, bnz, p0, lane, next, row);
+        gb_chunk_rows<UNI_WPI>(brp, nrows, bnz, p0, lane, next, row);
         bool only[UNI_WPI];
 #pragma unroll
         for (int u = 0; u < UNI_WPI; u++) {
@@ -141,7 +109,7 @@ __global__ __launch_bounds__(UNI_BLOCK) void k_union_fill_a(
     for (int64_t g = g0; g < g1; g++) {
         const int64_t p0 = (g * UNI_WPI) << 6;
         int64_t row[UNI_WPI];
-        uni_chunk_rows(arp, nrows, anz, p0, lane, next, row);
+        gb_chunk_rows<UNI_WPI>(arp, nrows, anz, p0, lane, next, row);
 #pragma unroll
         for (int u = 0; u < UNI_WPI; u++) {
             const int64_t p = p0 + u * 64 + lane;
@@ -187,7 +155,7 @@ __global__ __launch_bounds__(UNI_BLOCK) void k_union_fill_b(
         }
         if (!any) continue;  // the same in every lane; next stays a lower bound
         int64_t row[UNI_WPI];
-        uni_chunk_rows(brp, nrows, bnz, p0, lane, next, row);
+        gb_chunk_rows<UNI_WPI>(brp, nrows, bnz, p0, lane, next, row);
 #pragma unroll
         for (int u = 0; u < UNI_WPI; u++) {
             if (!((word[u] >> lane) & 1)) continue;  // a set bit is an entry below bnz (k_union_mark)
@@ -236,16 +204,10 @@ __global__ __launch_bounds__(UNI_BLOCK) void k_union_vec(int64_t n, int64_t nw, 
     gb_block_add(nb, stat + 2);
 }
 
-// the counters hold the last call's entries: gb_stat_add only adds
-void uni_stat_set(const char *name, int64_t v) {
-    int64_t old = 0;
-    gb_stat_get(name, &old);
-    gb_stat_add(name, v - old);
-}
 void uni_stats(int64_t both, int64_t a_only, int64_t b_only) {
-    uni_stat_set("union_both", both);
-    uni_stat_set("union_a_only", a_only);
-    uni_stat_set("union_b_only", b_only);
+    gb_stat_set("union_both", both);
+    gb_stat_set("union_a_only", a_only);
+    gb_stat_set("union_b_only", b_only);
 }
 
 // a vector call leaves its three counts here (device) until a reader asks

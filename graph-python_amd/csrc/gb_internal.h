@@ -189,6 +189,7 @@ extern std::atomic<int64_t> g_stat_host_push;  // SpMV launches whose push direc
 // GxB_Global_get_int("stat_<name>") reads them; tests assert that a workload reached a class
 void gb_stat_add(const char *name, int64_t v);
 bool gb_stat_get(const char *name, int64_t *v);
+void gb_stat_set(const char *name, int64_t v);  // a counter that holds the last call's figure
 
 // ------------------------------------------------------------------ deferred work (gb_bfs_loop.hip)
 // The level-BFS loop's host side defers three things -- a speculatively enqueued next level, a
@@ -612,6 +613,12 @@ void gb_ewise_union(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_BinaryOp add, 
 // GxB_Global_get_int asks here first: brings "stat_union_*" up to date after a vector call,
 // whose counts stay on the device until somebody reads them
 void gb_union_stat_refresh(const char *key);
+
+// concat / split (gb_tile.hip): the entry points are GxB_Matrix_concat / GxB_Matrix_split, which
+// leave "stat_concat_bitmap" / "stat_split_bitmap" / "stat_concat_iso" behind (gb_stat_set).
+// split builds its tiles around storage it computed: an object of this shape without storage
+// (gb_object.hip; the caller installs CSR or a bitmap, or frees it with gb_obj_free_storage)
+GB_Obj *gb_new_object_bare(int kind, GrB_Type type, int64_t nrows, int64_t ncols);
 
 // sort (gb_sort.hip): the entry points are GxB_Matrix_sort / GxB_Vector_sort; GxB_Global_get_int
 // asks here for "stat_sort_rows_{wave,block,long}" (rows each class took in the last matrix sort,

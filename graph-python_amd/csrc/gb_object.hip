@@ -57,7 +57,7 @@ static void alloc_empty_storage(GB_Obj *A) {
     A->iso = false;
 }
 
-GB_Obj *gb_new_object(int kind, GrB_Type type, int64_t nrows, int64_t ncols) {
+GB_Obj *gb_new_object_bare(int kind, GrB_Type type, int64_t nrows, int64_t ncols) {
     gb_require_init();
     GB_REQUIRE(type && type->magic == GB_MAGIC, GrB_UNINITIALIZED_OBJECT, "invalid type");
     GB_REQUIRE(nrows >= 0 && ncols >= 0, GrB_INVALID_VALUE, "negative dimension");
@@ -74,6 +74,11 @@ GB_Obj *gb_new_object(int kind, GrB_Type type, int64_t nrows, int64_t ncols) {
     A->type = type;
     A->nrows = nrows;
     A->ncols = ncols;
+    return A;
+}
+
+GB_Obj *gb_new_object(int kind, GrB_Type type, int64_t nrows, int64_t ncols) {
+    GB_Obj *A = gb_new_object_bare(kind, type, nrows, ncols);
     try {
         alloc_empty_storage(A);
     } catch (...) {

@@ -74,4 +74,5 @@ __all__ = ["Matrix", "Vector", "Scalar", "TransposedMatrix", "Recorder", "binary
 
 from . import dtypes  # noqa: E402
 from . import io  # noqa: E402,F401
+from . import ss  # noqa: E402,F401
 from .agg import agg  # noqa: E402

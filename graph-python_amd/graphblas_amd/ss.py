@@ -1,4 +1,4 @@
-"""``Vector.ss`` / ``Matrix.ss`` extension namespaces: the prefix scan and sort.
+"""``Vector.ss`` / ``Matrix.ss`` extension namespaces: the prefix scan, sort, split and concat.
 
 ``prefix_scan`` restates reference core/ss/prefix_scan.py:12-172: a
 Blelloch up-sweep / down-sweep expressed entirely as masked, accumulated
@@ -14,14 +14,19 @@ import of the same arrays).
 segmented sort on the device, nothing goes through the host.  The k largest
 entries of every row are ``C, P = A.ss.sort(">")`` followed by
 ``C.select("col<=", k - 1)`` (and the same select of ``P`` for where they came from).
+
+``split`` / ``concat`` are one call of GxB_Matrix_split / GxB_Matrix_concat (csrc/gb_tile.hip)
+whatever the number of tiles; vectors go through the same two entry points as N x 1 objects, as
+in the reference (core/ss/matrix.py:281-381, core/ss/vector.py:185-265, ss/_core.py:73-107).
 """
+import ctypes
 from math import ceil, log2
 
 import numpy as np
 
 from . import operator as _op
 from .base import call, descriptor_lookup
-from .dtypes import INT8, UINT64
+from .dtypes import INT8, UINT64, lookup_dtype, unify
 
 
 def _scan_monoid(x, op):
@@ -128,6 +133,194 @@ def prefix_scan(A, op, *, name=None):
     return Matrix.from_coo(rows, cols, rv, dtype=RV.dtype, nrows=A.nrows, ncols=A.ncols, name=name)
 
 
+# ---------------------------------------------------------------- split / concat
+def _integral(x):
+    """``x`` as an int when it is a whole number (int, numpy integer, float without fraction)."""
+    if isinstance(x, (int, np.integer)):
+        return int(x)
+    if isinstance(x, (float, np.floating)) and float(x).is_integer():
+        return int(x)
+    return None
+
+
+def _positive(c):
+    if c < 0:
+        raise ValueError(f"Chunksize must be greater than 0; got: {c}")
+    return c
+
+
+def _dimension_chunks(size, chunk, chunks):
+    """The chunk sizes of one dimension of length ``size``."""
+    if chunk is None:
+        return [size]
+    c = _integral(chunk)
+    if c is not None:
+        _positive(c)
+        full, rest = divmod(size, c)
+        return [c] * full + ([rest] if rest else [])
+    if isinstance(chunk, np.ndarray):
+        if not np.issubdtype(chunk.dtype, np.integer):
+            raise TypeError(f"numpy array for chunks must be integer dtype; got {chunk.dtype}")
+        if chunk.ndim != 1:
+            raise TypeError(f"numpy array for chunks must be 1-dimension; got ndim={chunk.ndim}")
+        if (chunk < 0).any():
+            raise ValueError(f"Chunksize must be greater than 0; got: {chunk[chunk < 0]}")
+        return chunk.tolist()
+    if not isinstance(chunk, (list, tuple)):
+        raise TypeError("Chunks for a dimension must be an integer, a list or tuple of integers, or None."
+                        f"  Got: {type(chunk)}")
+    sizes, rest_at = [], None
+    for item in chunk:
+        if item is None:
+            if rest_at is not None:
+                raise TypeError('None value in chunks for "the rest" can only appear once per dimension')
+            rest_at = len(sizes)
+            sizes.append(0)
+            continue
+        c = _integral(item)
+        if c is None:
+            raise TypeError(f"Bad type for element in chunks; expected int or None, but got: {type(chunks)}")
+        sizes.append(_positive(c))
+    if rest_at is not None:
+        rest = size - sum(sizes)
+        if rest < 0:
+            raise ValueError("Chunks are too large; None value in chunks would need to be negative "
+                             "to match size of input")
+        sizes[rest_at] = rest
+    return sizes
+
+
+def normalize_chunks(chunks, shape):
+    """The ``chunks`` argument of ``split`` as one list of sizes per dimension of ``shape``
+    (behaviour of reference core/utils.py:172-258).  Per dimension: an integer (equal chunks, the
+    last one smaller), a list or tuple of sizes with at most one ``None`` for "the rest", ``None``
+    (one chunk) or a 1-D integer numpy array; a single integer stands for every dimension.
+    Whether the sizes add up to the dimension is the library's check (DimensionMismatch)."""
+    whole = _integral(chunks)
+    if whole is not None:
+        chunks = (whole,) * len(shape)
+    elif isinstance(chunks, np.ndarray):
+        chunks = chunks.tolist()
+    elif not isinstance(chunks, (list, tuple)):
+        raise TypeError(f"chunks argument must be a list, tuple, or numpy array; got: {type(chunks)}")
+    if len(chunks) != len(shape):
+        kind = "Vector" if len(shape) == 1 else "Matrix"
+        raise ValueError(f"chunks argument must be of length {len(shape)} (one for each dimension of a {kind})")
+    return [_dimension_chunks(size, chunk, chunks) for size, chunk in zip(shape, chunks)]
+
+
+class _HandleArray:
+    """A ``GrB_Matrix[]`` argument; errors of the call are read from ``exc_arg`` when given."""
+
+    def __init__(self, count, name="tiles", exc_arg=None):
+        self.array = (ctypes.c_void_p * count)()
+        self.name = name
+        if exc_arg is not None:
+            self._exc_arg = exc_arg
+
+    @property
+    def _carg(self):
+        return ctypes.cast(self.array, ctypes.c_void_p)
+
+
+class _IndexArray:
+    def __init__(self, values, name):
+        self.array = (ctypes.c_uint64 * len(values))(*values)
+        self.name = name
+
+    @property
+    def _carg(self):
+        return ctypes.cast(self.array, ctypes.c_void_p)
+
+
+def _tile_kind(tile):
+    """2 for a Matrix or TransposedMatrix, 1 for a Vector or Scalar, 0 for anything else."""
+    from .matrix import Matrix, TransposedMatrix
+    from .scalar import Scalar
+    from .vector import Vector
+
+    if isinstance(tile, (Matrix, TransposedMatrix)):
+        return 2
+    return 1 if isinstance(tile, (Vector, Scalar)) else 0
+
+
+def _tile_shape(tile):
+    if _tile_kind(tile) == 2:
+        return tile._nrows, tile._ncols
+    return getattr(tile, "_size", 1), 1
+
+
+def _concat_tiles(tiles, is_matrix=None):
+    """Check the ``tiles`` argument of a concat: ``(rows of tiles, m, n, is_matrix)``.  A flat
+    list of vectors is a vector concat (unless ``is_matrix`` asks for a Matrix), a list of lists
+    a matrix concat in which vectors count as N x 1."""
+    if not isinstance(tiles, (list, tuple)):
+        raise TypeError(f"tiles argument must be list or tuple; got: {type(tiles)}")
+    if not tiles:
+        raise ValueError("tiles argument must not be empty")
+    rows, n = [], None
+    for i, row in enumerate(tiles):
+        if not isinstance(row, (list, tuple)):
+            if is_matrix or _tile_kind(row) != 1:
+                raise TypeError(f"tiles must be lists or tuples; got: {type(row)}")
+            is_matrix, n = False, 1
+            rows.append([row])
+            continue
+        if is_matrix is False:
+            raise TypeError(f"Bad tile type for concat at position {i}")
+        is_matrix = True
+        if n is None:
+            n = len(row)
+            if n == 0:
+                raise ValueError("tiles must not be empty")
+        elif len(row) != n:
+            raise ValueError(f"tiles must all be the same length; got tiles of length {n} and {len(row)}")
+        for j, tile in enumerate(row):
+            if _tile_kind(tile) == 0:
+                raise TypeError(f"Bad tile type for concat at position [{i}, {j}]; got: {type(tile)}")
+        rows.append(list(row))
+    return rows, len(rows), n, is_matrix
+
+
+def _concat_into(out, rows, m, n):
+    """GxB_Matrix_concat of the checked tiles into ``out`` (a Matrix or a Vector)."""
+    from .matrix import TransposedMatrix
+
+    ctiles = _HandleArray(m * n)
+    keep = []  # materialised transposes live until the call is over
+    for i, row in enumerate(rows):
+        for j, tile in enumerate(row):
+            if isinstance(tile, TransposedMatrix):
+                tile = tile.new()
+                keep.append(tile)
+            ctiles.array[i * n + j] = tile._h.value
+    call("GxB_Matrix_concat", [out, ctiles, m, n, None])
+
+
+def concat(tiles, dtype=None, *, name=None):
+    """GxB_Matrix_concat into a new object (reference ss/_core.py:73-107): a list of lists of
+    tiles gives a Matrix (vectors inside count as N x 1), a flat list of vectors a Vector.
+    ``dtype`` defaults to the type that holds every tile's."""
+    from .matrix import Matrix
+    from .vector import Vector
+
+    rows, m, n, is_matrix = _concat_tiles(tiles)
+    if dtype is None:
+        dtype = rows[0][0].dtype
+        for row in rows:
+            for tile in row:
+                dtype = unify(dtype, tile.dtype)
+    dtype = lookup_dtype(dtype)
+    nrows = sum(_tile_shape(row[0])[0] for row in rows)
+    if is_matrix:
+        ncols = sum(_tile_shape(tile)[1] for tile in rows[0])
+        out = Matrix(dtype, nrows, ncols, name=name)
+    else:
+        out = Vector(dtype, nrows, name=name)
+    _concat_into(out, rows, m, n)
+    return out
+
+
 _ORDERS = {"rowwise": "rowwise", "row": "rowwise", "rows": "rowwise", "c": "rowwise",
            "columnwise": "columnwise", "col": "columnwise", "cols": "columnwise", "column": "columnwise",
            "columns": "columnwise", "f": "columnwise"}
@@ -173,6 +366,31 @@ class VectorSS:
         call("GxB_Vector_sort", [w, p, op, parent, desc])
         return w, p
 
+    def split(self, chunks, *, name=None):
+        """GxB_Matrix_split of the vector as N x 1 (reference core/ss/vector.py:185-234): a list
+        of Vectors named ``f"{name}_{i}"``.  ``chunks``: see ``normalize_chunks``."""
+        from .vector import Vector
+
+        parent = self._parent
+        sizes, _ = normalize_chunks([chunks, None], (parent._size, 1))
+        m = len(sizes)
+        tiles = _HandleArray(m, exc_arg=parent)
+        call("GxB_Matrix_split", [tiles, m, 1, _IndexArray(sizes, "Tile_nrows"), _IndexArray([1], "Tile_ncols"),
+                                  parent, None])
+        name = parent.name if name is None else name
+        out = []
+        for i, size in enumerate(sizes):
+            w = Vector.__new__(Vector)
+            w.dtype, w.name, w._size = parent.dtype, f"{name}_{i}", size
+            w._h = ctypes.c_void_p(tiles.array[i])
+            out.append(w)
+        return out
+
+    def concat(self, tiles):
+        """GxB_Matrix_concat of a flat list of Vectors into this Vector, whose old contents are
+        discarded (reference core/ss/vector.py:251-267)."""
+        rows, m, n, _ = _concat_tiles(tiles, is_matrix=False)
+        _concat_into(self._parent, rows, m, n)
 
 class MatrixSS:
     def __init__(self, parent):
@@ -207,3 +425,32 @@ class MatrixSS:
         P = Matrix(UINT64, parent.nrows, parent.ncols, name="Permutation") if permutation else None
         call("GxB_Matrix_sort", [C, P, op, parent, desc])
         return C, P
+
+    def split(self, chunks, *, name=None):
+        """GxB_Matrix_split (reference core/ss/matrix.py:281-339): a list of lists of Matrix
+        tiles named ``f"{name}_{i}x{j}"``.  ``chunks``: see ``normalize_chunks``."""
+        from .matrix import Matrix
+
+        parent = self._parent
+        tile_nrows, tile_ncols = normalize_chunks(chunks, parent.shape)
+        m, n = len(tile_nrows), len(tile_ncols)
+        tiles = _HandleArray(m * n, exc_arg=parent)
+        call("GxB_Matrix_split", [tiles, m, n, _IndexArray(tile_nrows, "Tile_nrows"),
+                                  _IndexArray(tile_ncols, "Tile_ncols"), parent, None])
+        name = parent.name if name is None else name
+        out = []
+        for i, nrows in enumerate(tile_nrows):
+            row = []
+            for j, ncols in enumerate(tile_ncols):
+                T = Matrix.__new__(Matrix)
+                T.dtype, T.name, T._nrows, T._ncols = parent.dtype, f"{name}_{i}x{j}", nrows, ncols
+                T._h = ctypes.c_void_p(tiles.array[i * n + j])
+                row.append(T)
+            out.append(row)
+        return out
+
+    def concat(self, tiles):
+        """GxB_Matrix_concat of a list of lists of tiles into this Matrix, whose old contents are
+        discarded; Vectors count as N x 1 (reference core/ss/matrix.py:363-381)."""
+        rows, m, n, _ = _concat_tiles(tiles, is_matrix=True)
+        _concat_into(self._parent, rows, m, n)

@@ -354,6 +354,21 @@ GrB_Info GxB_Matrix_eWiseUnion(GrB_Matrix C, const GrB_Matrix Mask, const GrB_Bi
 GrB_Info GxB_Vector_eWiseUnion(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum,
                                const GrB_BinaryOp add, const GrB_Vector u, const GrB_Scalar alpha,
                                const GrB_Vector v, const GrB_Scalar beta, const GrB_Descriptor desc);
+/* concat / split (reference core/ss/matrix.py:281-381, core/ss/vector.py:185-265): tiling.  Tiles
+ * is row-major, tile (i, j) is Tiles[i * n + j]; no mask, no accumulator, the descriptor is
+ * checked and otherwise unused.  concat replaces C by the m x n tiles put together: every tile of
+ * tile-row i has the same number of rows, every tile of tile-column j the same number of
+ * columns, and the sums are C's shape (else GrB_DIMENSION_MISMATCH); values are cast to C's
+ * type; C may be one of the tiles; vectors and scalars count as N x 1 tiles and as C.  split
+ * creates m * n new matrices of A's type, tile (i, j) of Tile_nrows[i] x Tile_ncols[j] (the sums
+ * are A's shape); when A is a vector the tiles are vectors and n is 1; after a failure no handle
+ * is left allocated.  Tiles without rows or columns are legal in both; m == 0 or n == 0 is
+ * GrB_INVALID_VALUE. */
+GrB_Info GxB_Matrix_concat(GrB_Matrix C, const GrB_Matrix *Tiles, const GrB_Index m, const GrB_Index n,
+                           const GrB_Descriptor desc);
+GrB_Info GxB_Matrix_split(GrB_Matrix *Tiles, const GrB_Index m, const GrB_Index n,
+                          const GrB_Index *Tile_nrows, const GrB_Index *Tile_ncols, const GrB_Matrix A,
+                          const GrB_Descriptor desc);
 
 /* ---------------------------------------------------------------- the hot path */
 /* C<Mask> = C accum (A' (+).(x) B')      replaces SuiteSparse GrB_mxm */
@@ -540,7 +555,9 @@ GrB_Info GxB_MatrixMarket_free(void *p);
  * read back as their defaults while unset).  get_int also reads "stat_sort_rows_wave" /
  * "stat_sort_rows_block" / "stat_sort_rows_long" (rows each class took in the last sort),
  * "stat_union_both" / "stat_union_a_only" / "stat_union_b_only" (entries of T the last
- * eWiseUnion computed from both operands, from A' and beta, from alpha and B'), the read-only counters "stat_bfs_spec_adopted" / "stat_bfs_spec_rollbacks" (BFS level
+ * eWiseUnion computed from both operands, from A' and beta, from alpha and B'),
+ * "stat_concat_bitmap" / "stat_split_bitmap" (1 when the last concat / split moved bitmaps, 0
+ * when it built CSR), "stat_concat_iso" (1 when the last concat's result was iso), the read-only counters "stat_bfs_spec_adopted" / "stat_bfs_spec_rollbacks" (BFS level
  * speculation) and "stat_nvals_copy" (vector counts read by a device copy
  * instead of the producing kernel's host mailbox). */
 GrB_Info GxB_Global_set_int(const char *key, int64_t value);
