@@ -600,6 +600,12 @@ bool gb_zpool_clear_vector(GB_Obj *v);
 void gb_select(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_IndexUnaryOp op, GB_Obj *A, const void *y, int ycode,
                const gb_desc &d);
 
+// apply with an index-unary operator (gb_apply_index.hip): T = f(A'(i, j), i, j, *y) on the structure
+// of A' (BOOL for the select operators, the operator's type for ROWINDEX / COLINDEX / DIAGINDEX),
+// written back as C<M> = C accum T
+void gb_apply_index(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_IndexUnaryOp op, GB_Obj *A, const void *y, int ycode,
+                    const gb_desc &d);
+
 // kronecker (gb_kron.hip): T(iA p + iB, jA q + jB) = binop(A'(iA, jA), B'(iB, jB)) for every pair
 // of stored entries, written back as C<M> = C accum T
 void gb_kronecker(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_BinaryOp binop, GB_Obj *A, GB_Obj *B,

@@ -10,6 +10,8 @@
 //                                              core/matrix.py:2392,2435
 //   GrB_{Vector,Matrix}_select_Scalar          reference core/vector.py:1463-1560,
 //                                              core/matrix.py:2452-2551
+//   GrB_{Vector,Matrix}_apply_IndexOp_Scalar   reference core/matrix.py:2337-2437, core/vector.py
+//                                              (same method)
 //   GxB_{Vector,Matrix}_eWiseUnion             reference core/vector.py:1141-1260,
 //                                              core/matrix.py:2044-2161
 // Each reads the scalar's value (its own type) on the host and forwards to the typed entry
@@ -176,24 +178,31 @@ GrB_Info apply_scalar(bool vec, bool first, OUT w, const OUT mask, const GrB_Bin
     return GrB_DOMAIN_MISMATCH;
 }
 
-// select with the thunk in a GrB_Scalar
+// select, or apply with an index-unary operator, with the thunk in a GrB_Scalar
 template <class OUT>
-GrB_Info select_scalar(bool vec, OUT w, const OUT mask, const GrB_BinaryOp accum, const GrB_IndexUnaryOp op,
-                       const OUT u, const GrB_Scalar s, const GrB_Descriptor desc) {
+GrB_Info index_op_scalar(bool vec, bool apply, OUT w, const OUT mask, const GrB_BinaryOp accum,
+                         const GrB_IndexUnaryOp op, const OUT u, const GrB_Scalar s, const GrB_Descriptor desc) {
     sval v;
     GrB_Info e = read_scalar(v, s);
     if (e != GrB_SUCCESS) return e;
-    if (!v.present) return fail_on(w, GrB_EMPTY_OBJECT, "select: the thunk GrB_Scalar holds no value");
+    if (!v.present)
+        return fail_on(w, GrB_EMPTY_OBJECT, apply ? "apply: the thunk GrB_Scalar holds no value"
+                                                  : "select: the thunk GrB_Scalar holds no value");
     switch (v.code) {
-#define GB_SELECT(T, ctype)                                                                               \
-    case GBAMD_T_##T: {                                                                                   \
-        ctype c;                                                                                          \
-        std::memcpy(&c, v.bytes, sizeof(ctype));                                                          \
-        if (vec) return GrB_Vector_select_##T((GrB_Vector)w, (GrB_Vector)mask, accum, op, (GrB_Vector)u, c, desc); \
-        return GrB_Matrix_select_##T((GrB_Matrix)w, (GrB_Matrix)mask, accum, op, (GrB_Matrix)u, c, desc); \
+#define GB_INDEX_OP(T, ctype)                                                                                        \
+    case GBAMD_T_##T: {                                                                                              \
+        ctype c;                                                                                                     \
+        std::memcpy(&c, v.bytes, sizeof(ctype));                                                                     \
+        if (vec)                                                                                                     \
+            return apply ? GrB_Vector_apply_IndexOp_##T((GrB_Vector)w, (GrB_Vector)mask, accum, op, (GrB_Vector)u, c, \
+                                                        desc)                                                        \
+                         : GrB_Vector_select_##T((GrB_Vector)w, (GrB_Vector)mask, accum, op, (GrB_Vector)u, c, desc); \
+        return apply ? GrB_Matrix_apply_IndexOp_##T((GrB_Matrix)w, (GrB_Matrix)mask, accum, op, (GrB_Matrix)u, c,    \
+                                                    desc)                                                            \
+                     : GrB_Matrix_select_##T((GrB_Matrix)w, (GrB_Matrix)mask, accum, op, (GrB_Matrix)u, c, desc);   \
     }
-        GB_FOR_EACH_TYPE(GB_SELECT)
-#undef GB_SELECT
+        GB_FOR_EACH_TYPE(GB_INDEX_OP)
+#undef GB_INDEX_OP
     }
     return GrB_DOMAIN_MISMATCH;
 }
@@ -362,12 +371,23 @@ GrB_Info GrB_Matrix_apply_BinaryOp2nd_Scalar(GrB_Matrix C, const GrB_Matrix Mask
 GrB_Info GrB_Vector_select_Scalar(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum,
                                   const GrB_IndexUnaryOp op, const GrB_Vector u, const GrB_Scalar y,
                                   const GrB_Descriptor desc) {
-    return select_scalar(true, w, mask, accum, op, u, y, desc);
+    return index_op_scalar(true, false, w, mask, accum, op, u, y, desc);
 }
 GrB_Info GrB_Matrix_select_Scalar(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum,
                                   const GrB_IndexUnaryOp op, const GrB_Matrix A, const GrB_Scalar y,
                                   const GrB_Descriptor desc) {
-    return select_scalar(false, C, Mask, accum, op, A, y, desc);
+    return index_op_scalar(false, false, C, Mask, accum, op, A, y, desc);
+}
+
+GrB_Info GrB_Vector_apply_IndexOp_Scalar(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum,
+                                         const GrB_IndexUnaryOp op, const GrB_Vector u, const GrB_Scalar y,
+                                         const GrB_Descriptor desc) {
+    return index_op_scalar(true, true, w, mask, accum, op, u, y, desc);
+}
+GrB_Info GrB_Matrix_apply_IndexOp_Scalar(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum,
+                                         const GrB_IndexUnaryOp op, const GrB_Matrix A, const GrB_Scalar y,
+                                         const GrB_Descriptor desc) {
+    return index_op_scalar(false, true, C, Mask, accum, op, A, y, desc);
 }
 
 }  // extern "C"

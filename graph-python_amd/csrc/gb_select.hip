@@ -17,11 +17,13 @@
 //                     rowptr[i] == nvals may name the word after the last: it exists and is zero
 // Vectors (bitmap): k_select_vec, one lane per position, new word = ballot(bit & predicate);
 // the dense values are copied as they are.
+// The operators themselves are gb_indexop.cuh's, shared with gb_apply_index.hip; an index-valued one
+// (ROWINDEX, COLINDEX, DIAGINDEX) keeps the entries whose result is not zero.
 // T has A's type and values (the operator's type serves the comparison only); the write-back
 // (mask, replace, accum, cast to C's type) is gb_writeback_*, as for every operation.
 #include <algorithm>
 
-#include "gb_dispatch.cuh"
+#include "gb_indexop.cuh"
 #include "gb_internal.h"
 
 #define SEL_BLOCK 256
@@ -31,31 +33,6 @@
 namespace {
 
 enum { SEL_ROWCOL = 0, SEL_COL = 1, SEL_VALUE = 2 };
-
-GB_DEV bool sel_positional(int op, int64_t i, int64_t j, int64_t k) {
-    switch (op) {
-    case GBAMD_IOP_TRIL: return j <= i + k;
-    case GBAMD_IOP_TRIU: return j >= i + k;
-    case GBAMD_IOP_DIAG: return j == i + k;
-    case GBAMD_IOP_OFFDIAG: return j != i + k;
-    case GBAMD_IOP_COLLE: return j <= k;
-    case GBAMD_IOP_COLGT: return j > k;
-    case GBAMD_IOP_ROWLE: return i <= k;
-    default: return i > k;  // ROWGT
-    }
-}
-
-template <class X>
-GB_DEV bool sel_value(int op, X x, X y) {
-    switch (op) {
-    case GBAMD_IOP_VALUEEQ: return x == y;
-    case GBAMD_IOP_VALUENE: return x != y;
-    case GBAMD_IOP_VALUEGT: return x > y;
-    case GBAMD_IOP_VALUEGE: return x >= y;
-    case GBAMD_IOP_VALUELT: return x < y;
-    default: return x <= y;  // VALUELE
-    }
-}
 
 // words [0, nw1): nw1 = nvals / 64 + 1 covers every entry and leaves the last word's bits past
 // nvals (or a whole last word, when nvals is a multiple of 64) zero.  A wave owns a contiguous
@@ -105,12 +82,12 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_select_mark(int64_t nvals, int64_
             bool kp = false;
             if (p < nvals) {
                 if (MODE == SEL_VALUE) {
-                    kp = sel_value<X>(op, iso ? xiso : vals[p], y);
+                    kp = gb_iop_value<X>(op, iso ? xiso : vals[p], y);
                 } else {
                     const int64_t j = colidx[p];
                     int64_t i = 0;
                     if (MODE == SEL_ROWCOL) i = (nb >= 0 ? rlo + below[u] : gb_upper_bound(rowptr, rlo, rhi, p)) - 1;
-                    kp = sel_positional(op, i, j, k);
+                    kp = gb_iop_positional(op, i, j, k, (int64_t)y);
                 }
             }
             keep[u] = kp;
@@ -179,27 +156,12 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_select_vec(int64_t n, int64_t nw,
         const int64_t i = (w << 6) + lane;
         bool kp = false;
         if (i < n && ((bits[w] >> lane) & 1)) {
-            if (VALUE) kp = sel_value<X>(op, vals[iso ? 0 : i], y);
-            else kp = sel_positional(op, i, 0, k);
+            if (VALUE) kp = gb_iop_value<X>(op, vals[iso ? 0 : i], y);
+            else kp = gb_iop_positional(op, i, 0, k, (int64_t)y);
         }
         const unsigned long long b = __ballot(kp);
         if (lane == 0) obits[w] = b;
     }
-}
-
-// the thunk *y (type ycode) cast to T, the type of code tcode
-template <class T>
-T sel_thunk(const void *y, int ycode, int tcode) {
-    T out = T();
-    gb_cast_scalar(&out, tcode, y, ycode);
-    return out;
-}
-
-// the thunk of a positional operator: |k| beyond any index distance decides the same way, and
-// the clamp keeps i + k from overflowing
-int64_t sel_thunk_k(const void *y, int ycode) {
-    const int64_t lim = (int64_t)1 << 61;
-    return std::min(std::max(sel_thunk<int64_t>(y, ycode, GBAMD_T_INT64), -lim), lim);
 }
 
 void select_vector(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_IndexUnaryOp op, GB_Obj *A, const void *y, int ycode,
@@ -221,12 +183,14 @@ void select_vector(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_IndexUnaryOp op
                 using X = decltype(xv);
                 hipLaunchKernelGGL((k_select_vec<true, X>), dim3(grid), dim3(SEL_BLOCK), 0, gb_stream(), uv.n, nw,
                                    op->opcode, uv.bits, (const X *)xin, uv.iso, (int64_t)0,
-                                   sel_thunk<X>(y, ycode, op->xtype->code), T.bits);
+                                   gb_iop_thunk<X>(y, ycode, op->xtype->code), T.bits);
             });
         } else {
+            // a positional launch has no value thunk: its y carries the bits of an index-valued result
+            int64_t zmask;
+            const int64_t k = gb_iop_thunk_pos(op->opcode, y, ycode, op->ytype->code, &zmask);
             hipLaunchKernelGGL((k_select_vec<false, int64_t>), dim3(grid), dim3(SEL_BLOCK), 0, gb_stream(), uv.n, nw,
-                               op->opcode, uv.bits, (const int64_t *)nullptr, false, sel_thunk_k(y, ycode), (int64_t)0,
-                               T.bits);
+                               op->opcode, uv.bits, (const int64_t *)nullptr, false, k, zmask, T.bits);
         }
         GB_LAUNCH_CHECK();
         gb_copy_d2d(T.dense, uv.vals, nv * vs);
@@ -265,21 +229,21 @@ void select_matrix(GB_Obj *C, GB_Obj *M, GrB_BinaryOp accum, GrB_IndexUnaryOp op
                 using X = decltype(xv);
                 hipLaunchKernelGGL((k_select_mark<SEL_VALUE, X>), dim3(grid), dim3(SEL_BLOCK), 0, gb_stream(),
                                    v.nvals, v.nrows, nw1, op->opcode, v.rowptr, v.colidx, (const X *)xin, v.iso,
-                                   (int64_t)0, sel_thunk<X>(y, ycode, op->xtype->code), words, cnt);
+                                   (int64_t)0, gb_iop_thunk<X>(y, ycode, op->xtype->code), words, cnt);
             });
         } else {
-            const int64_t k = sel_thunk_k(y, ycode);
+            // a positional launch has no value thunk: its y carries the bits of an index-valued result
+            int64_t zmask;
             const int o = op->opcode;
-            const bool rows = o == GBAMD_IOP_TRIL || o == GBAMD_IOP_TRIU || o == GBAMD_IOP_DIAG ||
-                              o == GBAMD_IOP_OFFDIAG || o == GBAMD_IOP_ROWLE || o == GBAMD_IOP_ROWGT;
-            if (rows)
+            const int64_t k = gb_iop_thunk_pos(o, y, ycode, op->ytype->code, &zmask);
+            if (gb_iop_needs_row(o))
                 hipLaunchKernelGGL((k_select_mark<SEL_ROWCOL, int64_t>), dim3(grid), dim3(SEL_BLOCK), 0, gb_stream(),
                                    v.nvals, v.nrows, nw1, o, v.rowptr, v.colidx, (const int64_t *)nullptr, false, k,
-                                   (int64_t)0, words, cnt);
+                                   zmask, words, cnt);
             else
                 hipLaunchKernelGGL((k_select_mark<SEL_COL, int64_t>), dim3(grid), dim3(SEL_BLOCK), 0, gb_stream(),
                                    v.nvals, v.nrows, nw1, o, v.rowptr, v.colidx, (const int64_t *)nullptr, false, k,
-                                   (int64_t)0, words, cnt);
+                                   zmask, words, cnt);
         }
         GB_LAUNCH_CHECK();
         gb_exclusive_scan_u8(cnt, base, nw1);

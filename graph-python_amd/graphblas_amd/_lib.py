@@ -94,6 +94,7 @@ _SIGS = {
     "GrB_Vector_apply_BinaryOp1st_Scalar": [P] * 7, "GrB_Vector_apply_BinaryOp2nd_Scalar": [P] * 7,
     "GrB_Matrix_apply_BinaryOp1st_Scalar": [P] * 7, "GrB_Matrix_apply_BinaryOp2nd_Scalar": [P] * 7,
     "GrB_Matrix_select_Scalar": [P] * 7, "GrB_Vector_select_Scalar": [P] * 7, "GrB_IndexUnaryOp_free": [P],
+    "GrB_Matrix_apply_IndexOp_Scalar": [P] * 7, "GrB_Vector_apply_IndexOp_Scalar": [P] * 7,
 }
 for _t in TYPE_NAMES:
     _T = _CTYPES[_t]
@@ -122,6 +123,8 @@ for _t in TYPE_NAMES:
         f"GrB_Matrix_apply_BinaryOp2nd_{_t}": [P, P, P, P, P, _T, P],
         f"GrB_Matrix_select_{_t}": [P, P, P, P, P, _T, P],
         f"GrB_Vector_select_{_t}": [P, P, P, P, P, _T, P],
+        f"GrB_Matrix_apply_IndexOp_{_t}": [P, P, P, P, P, _T, P],
+        f"GrB_Vector_apply_IndexOp_{_t}": [P, P, P, P, P, _T, P],
     })
 
 # GrB_Info codes (C API 2.0; include/graphblas_amd.h)
@@ -182,7 +185,7 @@ class _Lib:
     def __dir__(self):
         names = list(_SIGS) + list(INFO) + list(ENUMS)
         names += [f"GrB_{t}" for t in TYPE_NAMES]
-        names += list(_builtins.BINOPS) + list(_builtins.UNOPS) + list(_builtins.INDEXUNARYOPS) + list(_builtins.MONOIDS) + list(_builtins.DESCRIPTORS.values())
+        names += list(_builtins.BINOPS) + list(_builtins.UNOPS) + list(_builtins.INDEXUNARYOPS) + list(_builtins.INDEXVALUEOPS) + list(_builtins.MONOIDS) + list(_builtins.DESCRIPTORS.values())
         for k, v in _builtins.SEMIRINGS.items():
             names.append(k)
             names.extend(v[2])

@@ -637,12 +637,16 @@ def _reduce_scalar(x, op, allow_empty):
 
 def _apply_expr(x, op, right, left):
     """x.apply(op[, right= | left=]) (reference core/vector.py:1311-1460, core/matrix.py:2297-2447):
-    a UnaryOp -> GrB_*_apply; a BinaryOp with a bound scalar -> GrB_*_apply_BinaryOp{1st,2nd}_<T>."""
+    a UnaryOp -> GrB_*_apply; a BinaryOp with a bound scalar -> GrB_*_apply_BinaryOp{1st,2nd}_<T>;
+    an index-unary or select operator (or "rowindex" / "colindex" / "diagindex" / "index") with the
+    thunk in `right` -> GrB_*_apply_IndexOp_<T>."""
     from .scalar import Scalar
     from .vector import VectorExpression
 
     kind = "Vector" if x.ndim == 1 else "Matrix"
     src, at = _unwrap(x) if kind == "Matrix" else (x, False)
+    if _is_index_unary(op):
+        return _apply_index_expr(x, kind, src, at, op, right, left)
 
     def mk(cf, args, t):
         if kind == "Vector":
@@ -672,6 +676,61 @@ def _apply_expr(x, op, right, left):
     if right is None:
         return mk(f"GrB_{kind}_apply_BinaryOp1st_{sc.dtype.name}", [cv, src], t)
     return mk(f"GrB_{kind}_apply_BinaryOp2nd_{sc.dtype.name}", [src, cv], t)
+
+
+def _is_index_unary(op):
+    """An index-unary or select operator, typed or not, or one of the names only `indexunary` has
+    (any other string in apply, "==" included, names a unary or binary operator)."""
+    if isinstance(op, str):
+        return op.strip().lower() in _op._INDEXUNARY_STRINGS
+    return getattr(op, "opclass", None) in ("IndexUnaryOp", "SelectOp")
+
+
+def _thunk_arg(thunk, kind, method, cname):
+    """-> (thunk dtype, C function, argument): a Scalar goes to GrB_<kind>_<cname>_Scalar, a literal
+    as a C scalar of its numpy type to the typed entry point (no GrB_Scalar)."""
+    from .scalar import Scalar
+
+    if isinstance(thunk, Scalar):
+        return thunk.dtype, f"GrB_{kind}_{cname}_Scalar", thunk
+    try:
+        a = np.asarray(thunk)
+        if a.ndim != 0:
+            raise TypeError("not a scalar")
+        tdtype = lookup_dtype(a.dtype)
+    except (TypeError, ValueError) as exc:
+        raise TypeError(f"Bad type for keyword argument `thunk` in {method}: {type(thunk)}; expected a "
+                        "Scalar or a literal scalar") from exc
+    return tdtype, f"GrB_{kind}_{cname}_{tdtype.name}", a.item()
+
+
+def _apply_index_expr(x, kind, src, at, op, right, left):
+    """x.apply(indexunary op, thunk) (reference core/matrix.py:2337-2437, core/vector.py, same
+    method): f(x(i, j), i, j, thunk) on the structure of x -> GrB_*_apply_IndexOp_<T> (a Scalar
+    thunk: GrB_*_apply_IndexOp_Scalar)."""
+    from .scalar import Scalar
+    from .vector import VectorExpression
+
+    if left is not None:
+        raise TypeError("Do not use `left` with an IndexUnaryOp or SelectOp in apply; "
+                        "the thunk goes to `right`")
+    thunk = right
+    if thunk is None:
+        thunk = False  # the most basic form of 0 when unifying dtypes
+    tdtype, cf, arg = _thunk_arg(thunk, kind, "apply", "apply_IndexOp")
+    if isinstance(op, str):
+        op = _op.indexunary.from_string(op)
+    if op.is_positional:
+        # typed by the input alone: INT32 -> the INT32 operator, anything else -> INT64
+        t = _op.get_typed_op(op, x.dtype, kind="indexunary")
+        if not isinstance(thunk, Scalar):
+            # the library casts the thunk of a positional operator to an integer
+            arg, cf = int(arg), f"GrB_{kind}_apply_IndexOp_INT64"
+    else:
+        t = _op.get_typed_op(op, x.dtype, tdtype, kind="indexunary", is_right_scalar=True)
+    if kind == "Vector":
+        return VectorExpression("apply", cf, [src, arg], op=t, size=x.size)
+    return MatrixExpression("apply", cf, [src, arg], op=t, at=at, nrows=x.nrows, ncols=x.ncols)
 
 
 def _select_mask(updater, obj, mask):
@@ -713,21 +772,12 @@ def _select_expr(x, op, thunk):
         return mk(None, [obj, mask, _select_mask, (obj, mask)])
     if thunk is None:
         thunk = False  # the most basic form of 0 when unifying dtypes
-    if isinstance(thunk, Scalar):
-        tdtype, cf, arg = thunk.dtype, f"GrB_{kind}_select_Scalar", thunk
+    tdtype, cf, arg = _thunk_arg(thunk, kind, "select", "select")
+    if getattr(op, "opclass", None) == "IndexUnaryOp" and op.is_positional:
+        t = _op.get_typed_op(op, x.dtype)  # rowindex / colindex / diagindex: typed by the input alone
     else:
-        # a literal: a C scalar of its numpy type, handed to the typed entry point (no GrB_Scalar)
-        try:
-            a = np.asarray(thunk)
-            if a.ndim != 0:
-                raise TypeError("not a scalar")
-            tdtype = lookup_dtype(a.dtype)
-        except (TypeError, ValueError) as exc:
-            raise TypeError(f"Bad type for keyword argument `thunk` in select: {type(thunk)}; expected a "
-                            "Scalar or a literal scalar") from exc
-        arg, cf = a.item(), f"GrB_{kind}_select_{tdtype.name}"
-    t = _op.get_typed_op(op, x.dtype, tdtype, kind="select", is_right_scalar=True)
-    if t.opclass != "SelectOp":
+        t = _op.get_typed_op(op, x.dtype, tdtype, kind="select", is_right_scalar=True)
+    if t.opclass not in ("SelectOp", "IndexUnaryOp"):
         raise TypeError(f"Bad type for argument `op` in select: expected SelectOp, got {t.opclass}")
     if t.is_positional and not isinstance(thunk, Scalar):
         # the library casts the thunk of a positional operator to INT64

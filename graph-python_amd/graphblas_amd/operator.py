@@ -127,6 +127,43 @@ def _call_select(opobj, expr, thunk):
     return expr.select(opobj, thunk)
 
 
+class TypedIndexUnaryOp(TypedOp):
+    """One dtype's view of an IndexUnaryOp."""
+
+    __slots__ = ()
+
+    def __call__(self, expr, thunk=None):
+        return _call_indexunary(self, expr, thunk)
+
+    def __reduce__(self):
+        return (_indexunary_lookup, (self.parent.name, self.type.name))
+
+
+class IndexUnaryOp(OpBase):
+    """A GrB_IndexUnaryOp used as a value producer (reference core/operator/indexunary.py):
+    indexunary.rowindex(A) is A.apply(indexunary.rowindex), indexunary.valueeq(A, s) is
+    A.apply(indexunary.valueeq, s)."""
+
+    opclass = "IndexUnaryOp"
+
+    def __call__(self, expr, thunk=None):
+        return _call_indexunary(self, expr, thunk)
+
+    def __reduce__(self):
+        return (_indexunary_lookup, (self.name, None))
+
+
+def _indexunary_lookup(name, dtype):
+    obj = getattr(indexunary, name)
+    return obj if dtype is None else obj[dtype]
+
+
+def _call_indexunary(opobj, expr, thunk):
+    if not hasattr(expr, "apply"):
+        raise TypeError(f"Bad type when calling {opobj!r}: {type(expr)}")
+    return expr.apply(opobj, thunk)
+
+
 class Monoid(OpBase):
     opclass = "Monoid"
 
@@ -189,7 +226,28 @@ for _gb, (_op, _t) in _builtins.INDEXUNARYOPS.items():
 # the vector names of the row operators (reference core/operator/select.py)
 select.indexle = select.rowle
 select.indexgt = select.rowgt
+# indexunary: the same operators as value producers (GrB_apply with an index-unary operator).
+# The positional select operators are the very objects of `select` (indexunary.tril is
+# select.tril; calling one selects).  The value operators are IndexUnaryOps of their own, so that
+# indexunary.valueeq(A, s) applies where select.valueeq(A, s) selects, as in the reference.
+# rowindex / colindex / diagindex (and index, the vector name of rowindex) live here only.
 indexunary = _Namespace(**select.__dict__)
+for _gb, (_op, _t) in _builtins.INDEXUNARYOPS.items():
+    if _t is None:
+        continue
+    _pyname = _op.lower()
+    _o = getattr(indexunary, _pyname)
+    if not isinstance(_o, IndexUnaryOp):
+        _o = IndexUnaryOp(_pyname)
+        setattr(indexunary, _pyname, _o)
+    _o._add(TypedIndexUnaryOp(_o, _pyname, lookup_dtype(_t), BOOL, _gb, "IndexUnaryOp"))
+for _gb, (_op, _t) in _builtins.INDEXVALUEOPS.items():
+    _pyname = _op.lower()
+    _o = _get(indexunary, IndexUnaryOp, _pyname)
+    _o.is_positional = True
+    _dt = lookup_dtype(_t)
+    _o._add(TypedIndexUnaryOp(_o, _pyname, _dt, _dt, _gb, "IndexUnaryOp"))
+indexunary.index = indexunary.rowindex
 
 for _gb, (_m, _t, _bop) in _builtins.MONOIDS.items():
     _pyname = "eq" if _gb == "GxB_EQ_BOOL_MONOID" else _m.lower()
@@ -258,6 +316,9 @@ for _opname, _target in [("max_first", "lor_first"), ("max_second", "lor_second"
 # positional binary ops on non-integer inputs use the INT64 version
 for _r in ["firsti", "firsti1", "firstj", "firstj1", "secondi", "secondi1", "secondj", "secondj1"]:
     _coerce(getattr(binary, _r), _POSDT, INT64)
+# and so do the index-valued index-unary operators
+for _r in ["rowindex", "colindex", "diagindex"]:
+    _coerce(getattr(indexunary, _r), _POSDT, INT64)
 
 # monoid coercions (reference core/operator/monoid.py:396-431): bool max/min/times are lor/land/land;
 # the logical monoids on numeric inputs use the BOOL monoid (values cast to bool)
@@ -346,13 +407,31 @@ def _select_from_string(s):
     return obj[dt] if dt else obj
 
 
+_INDEXUNARY_STRINGS = ("rowindex", "colindex", "diagindex", "index")
+
+
+def _indexunary_from_string(s):
+    """The select strings, read in the indexunary namespace, and the names that exist only there."""
+    name = s.strip()
+    dt = None
+    if name.endswith("]") and "[" in name:
+        name, dt = name[:-1].split("[", 1)
+    name = _SELECT_STRINGS.get(name, name).lower()
+    obj = getattr(indexunary, name, None)
+    if not isinstance(obj, (SelectOp, IndexUnaryOp)):
+        raise ValueError(f"Unknown indexunary string: {s!r}")
+    return obj[dt] if dt else obj
+
+
 select.from_string = _select_from_string
-indexunary.from_string = _select_from_string
+indexunary.from_string = _indexunary_from_string
 
 
 def _from_string(s, kind):
     if kind == "select":
         return _select_from_string(s)
+    if kind == "indexunary":
+        return _indexunary_from_string(s)
     name = s.strip()
     dt = None
     if name.endswith("]") and "[" in name:

@@ -204,7 +204,11 @@ GrB_Info GrB_Matrix_exportHint(GrB_Format *format, GrB_Matrix A);
                                               const GrB_Descriptor desc);                       \
     GrB_Info GrB_Matrix_select_##T(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, \
                                    const GrB_IndexUnaryOp op, const GrB_Matrix A, ctype y,      \
-                                   const GrB_Descriptor desc);
+                                   const GrB_Descriptor desc);                                  \
+    GrB_Info GrB_Matrix_apply_IndexOp_##T(GrB_Matrix C, const GrB_Matrix Mask,                  \
+                                          const GrB_BinaryOp accum, const GrB_IndexUnaryOp op,  \
+                                          const GrB_Matrix A, ctype y,                          \
+                                          const GrB_Descriptor desc);
 
 #define GB_DECLARE_TYPED_VECTOR(T, ctype)                                                          \
     GrB_Info GrB_Vector_build_##T(GrB_Vector w, const GrB_Index *I, const ctype *X,             \
@@ -232,7 +236,11 @@ GrB_Info GrB_Matrix_exportHint(GrB_Format *format, GrB_Matrix A);
                                               const GrB_Descriptor desc);                       \
     GrB_Info GrB_Vector_select_##T(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum, \
                                    const GrB_IndexUnaryOp op, const GrB_Vector u, ctype y,      \
-                                   const GrB_Descriptor desc);
+                                   const GrB_Descriptor desc);                                  \
+    GrB_Info GrB_Vector_apply_IndexOp_##T(GrB_Vector w, const GrB_Vector mask,                  \
+                                          const GrB_BinaryOp accum, const GrB_IndexUnaryOp op,  \
+                                          const GrB_Vector u, ctype y,                          \
+                                          const GrB_Descriptor desc);
 
 #define GB_FOR_EACH_TYPE(X)                                                                        \
     X(BOOL, bool)                                                                                  \
@@ -316,6 +324,18 @@ GrB_Info GrB_Matrix_select_Scalar(GrB_Matrix C, const GrB_Matrix Mask, const GrB
 GrB_Info GrB_Vector_select_Scalar(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum,
                                   const GrB_IndexUnaryOp op, const GrB_Vector u, const GrB_Scalar y,
                                   const GrB_Descriptor desc);
+/* apply with an index-unary operator (reference core/matrix.py:2337-2437, core/vector.py, same
+ * method): C<M> = accum(C, f(A'(i, j), i, j, y)) on exactly the structure of A' (a vector entry is
+ * at (i, 0)).  GrB_ROWINDEX / GrB_COLINDEX / GrB_DIAGINDEX_<INT32|INT64> store i + y, j + y,
+ * j - i + y (y cast to the operator's type; the sum taken in 64 bits, then cast to it); the select
+ * operators store their predicate as BOOL.  An empty y is GrB_EMPTY_OBJECT.  GrB_select with an
+ * index-valued operator keeps the entries whose result is not zero. */
+GrB_Info GrB_Matrix_apply_IndexOp_Scalar(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum,
+                                         const GrB_IndexUnaryOp op, const GrB_Matrix A, const GrB_Scalar y,
+                                         const GrB_Descriptor desc);
+GrB_Info GrB_Vector_apply_IndexOp_Scalar(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum,
+                                         const GrB_IndexUnaryOp op, const GrB_Vector u, const GrB_Scalar y,
+                                         const GrB_Descriptor desc);
 /* kronecker (reference core/matrix.py:2253-2292): C<M> = accum(C, kron(A', B')).  With A' m x n
  * and B' p x q (after GrB_INP0 / GrB_INP1), every pair of stored entries gives
  * T(iA p + iB, jA q + jB) = op(A'(iA, jA), B'(iB, jB)): the operands are cast to the operator's

@@ -62,7 +62,11 @@ UCODE = {n: i for i, n in enumerate(UNOPS)}
 # ones are untyped, the VALUE* ones compare the entry with the thunk in the operator's type
 IDXOPS_POSITIONAL = ["TRIL", "TRIU", "DIAG", "OFFDIAG", "COLLE", "COLGT", "ROWLE", "ROWGT"]
 IDXOPS_VALUE = ["VALUEEQ", "VALUENE", "VALUEGT", "VALUEGE", "VALUELT", "VALUELE"]
-IDXOPS = IDXOPS_POSITIONAL + IDXOPS_VALUE
+# the index-unary operators that produce an index, not a predicate (GrB_apply's ROWINDEX / COLINDEX /
+# DIAGINDEX, reference core/operator/indexunary.py:98-114): positional, typed by their result.
+# Their codes come after the select operators', which keep their numbers
+IDXOPS_INDEX = ["ROWINDEX", "COLINDEX", "DIAGINDEX"]
+IDXOPS = IDXOPS_POSITIONAL + IDXOPS_VALUE + IDXOPS_INDEX
 ICODE = {n: i for i, n in enumerate(IDXOPS)}
 
 MONOIDS = ["PLUS", "TIMES", "MIN", "MAX", "ANY", "LOR", "LAND", "LXOR", "LXNOR",
@@ -185,6 +189,11 @@ def idxop_table():
     return out
 
 
+def idxvalue_table():
+    """-> list of (name, opcode name, result type): positional, the thunk has the result's type."""
+    return [(f"GrB_{op}_{t}", op, t) for op in IDXOPS_INDEX for t in ["INT32", "INT64"]]
+
+
 def monoid_table():
     """-> list of (name, monoid code name, type, binop name)."""
     out = []
@@ -265,6 +274,7 @@ def main():
     binops = binop_table()
     unops = unop_table()
     idxops = idxop_table()
+    idxvals = idxvalue_table()
     monoids = monoid_table()
     semirings = semiring_table(binops, monoids)
     bmap = {b[0]: b for b in binops}
@@ -283,7 +293,8 @@ def main():
     for i, n in enumerate(UNOPS):
         lines.append(f"    GBAMD_UOP_{n} = {i},\n")
     lines.append(f"    GBAMD_UOP_COUNT = {len(UNOPS)}\n}};\n")
-    lines.append("/* index-unary (select) operator codes: positional first, then value */\n"
+    lines.append("/* index-unary operator codes: the select operators (positional first, then value), then the\n"
+                 " * index-valued operators of GrB_apply */\n"
                  "enum gbamd_idxop_code {\n")
     for i, n in enumerate(IDXOPS):
         lines.append(f"    GBAMD_IOP_{n} = {i},\n")
@@ -308,6 +319,9 @@ def main():
         d.append(f"GB_EXTERN GrB_UnaryOp {u[0]};\n")
     d.append("/* builtin index-unary operators (reference core/operator/indexunary.py:98-114) */\n")
     for u in idxops:
+        d.append(f"GB_EXTERN GrB_IndexUnaryOp {u[0]};\n")
+    d.append("/* builtin index-valued index-unary operators (GrB_apply; GrB_select keeps z != 0) */\n")
+    for u in idxvals:
         d.append(f"GB_EXTERN GrB_IndexUnaryOp {u[0]};\n")
     d.append("/* builtin monoids (reference core/operator/monoid.py:179-195) */\n")
     for m in monoids:
@@ -337,6 +351,8 @@ def main():
         x = f"&T_{u[2]}" if u[2] else "nullptr"
         y = f"&T_{u[2]}" if u[2] else "&T_INT64"
         c.append(f"GB_IndexUnaryOp_opaque I_{u[0]} = {{GB_MAGIC, GBAMD_IOP_{u[1]}, {x}, {y}, \"{u[0]}\"}};\n")
+    for u in idxvals:
+        c.append(f"GB_IndexUnaryOp_opaque I_{u[0]} = {{GB_MAGIC, GBAMD_IOP_{u[1]}, nullptr, &T_{u[2]}, \"{u[0]}\"}};\n")
     for m in monoids:
         c.append(f"GB_Monoid_opaque M_{m[0]} = {{GB_MAGIC, GBAMD_MON_{m[1]}, &T_{m[2]}, &B_{m[3]}, \"{m[0]}\"}};\n")
     for s in semirings:
@@ -353,7 +369,7 @@ def main():
         c.append(f"GrB_BinaryOp {b[0]} = &B_{b[0]};\n")
     for u in unops:
         c.append(f"GrB_UnaryOp {u[0]} = &U_{u[0]};\n")
-    for u in idxops:
+    for u in idxops + idxvals:
         c.append(f"GrB_IndexUnaryOp {u[0]} = &I_{u[0]};\n")
     for m in monoids:
         c.append(f"GrB_Monoid {m[0]} = &M_{m[0]};\n")
@@ -380,7 +396,7 @@ def main():
         c.append(f"    {{\"{name}\", 4, (void*)&D_{name}}},\n")
     for u in unops:
         c.append(f"    {{\"{u[0]}\", 5, (void*)&U_{u[0]}}},\n")
-    for u in idxops:
+    for u in idxops + idxvals:
         c.append(f"    {{\"{u[0]}\", 6, (void*)&I_{u[0]}}},\n")
     c.append("    {nullptr, -1, nullptr}\n};\n")
     _write_if_changed(os.path.join(ROOT, "graph-python_amd", "csrc", "gb_builtins.cpp"), "".join(c))
@@ -402,6 +418,9 @@ def main():
     p.append("}\n\n# name: (opcode name, type or None for positional)\nINDEXUNARYOPS = {\n")
     for u in idxops:
         p.append(f"    {u[0]!r}: ({u[1]!r}, {u[2]!r}),\n")
+    p.append("}\n\n# the index-valued index-unary operators -- name: (opcode name, result type)\nINDEXVALUEOPS = {\n")
+    for u in idxvals:
+        p.append(f"    {u[0]!r}: ({u[1]!r}, {u[2]!r}),\n")
     p.append("}\n\n# name: (monoid code name, type, binop name)\nMONOIDS = {\n")
     for m in monoids:
         p.append(f"    {m[0]!r}: ({m[1]!r}, {m[2]!r}, {m[3]!r}),\n")
@@ -413,7 +432,7 @@ def main():
         p.append(f"    {k!r}: {v!r},\n")
     p.append("}\n")
     _write_if_changed(os.path.join(ROOT, "graph-python_amd", "graphblas_amd", "_builtins.py"), "".join(p))
-    print(f"types={len(TYPES)} binops={len(binops)} unops={len(unops)} idxops={len(idxops)} monoids={len(monoids)} "
+    print(f"types={len(TYPES)} binops={len(binops)} unops={len(unops)} idxops={len(idxops)}+{len(idxvals)} monoids={len(monoids)} "
           f"semirings={len(semirings)} (+{sum(len(s[3]) for s in semirings)} aliases) "
           f"descriptors={len(DESCS)}")
 
