@@ -271,6 +271,7 @@ void gb_get_csc(gb_csr_view &v, GB_Obj *A) {
             gb_transpose_csr(A->nrows, A->ncols, A->nvals, A->rowptr, A->colidx, A->vals,
                              A->type->size, A->iso, &A->t_rowptr, &A->t_colidx, &A->t_vals);
             A->t_valid = true;
+            gb_stat_add("transposes_cached", 1);  // tests assert that an operation built none
         }
         v.nrows = A->ncols;
         v.ncols = A->nrows;

@@ -68,6 +68,9 @@ _SIGS = {
     "GxB_Matrix_sort": [P] * 5, "GxB_Vector_sort": [P] * 5,
     "GxB_Matrix_eWiseUnion": [P] * 9, "GxB_Vector_eWiseUnion": [P] * 9,
     "GxB_Matrix_concat": [P, P, I, I, P], "GxB_Matrix_split": [P, I, I, P, P, P, P],
+    "GrB_Matrix_diag": [P, P, L], "GxB_Matrix_diag": [P, P, L, P], "GxB_Vector_diag": [P, P, L, P],
+    "GxB_Matrix_reshape": [P, ctypes.c_bool, I, I, P], "GxB_Matrix_reshapeDup": [P, P, ctypes.c_bool, I, I, P],
+    "GxB_Vector_flatten": [P, P, ctypes.c_bool, P],
     "GrB_Vector_assign": [P, P, P, P, P, I, P], "GrB_Matrix_assign": [P, P, P, P, P, I, P, I, P],
     "GrB_Matrix_reduce_Monoid_Scalar": [P] * 5, "GrB_Vector_reduce_Monoid_Scalar": [P] * 5,
     "GrB_transpose": [P] * 5,

@@ -27,6 +27,7 @@ import numpy as np
 
 from . import operator as _op
 from .dtypes import FP64, INT64, lookup_dtype
+from .exceptions import DimensionMismatch
 
 
 def _chain_types(ops, initdtype):
@@ -275,11 +276,10 @@ def _one_vector(dtype, value):
 
 
 def _diag_of(w, n):
-    """diag(w) as an n x n Matrix (reference uses Vector.diag(), agg.py:494)."""
-    from .matrix import Matrix
-
-    idx, vals = w.to_coo()
-    return Matrix.from_coo(idx, idx, vals, dtype=w.dtype, nrows=n, ncols=n)
+    """diag(w) as an n x n Matrix: Vector.diag(), on the device (reference agg.py:494)."""
+    if w.size != n:
+        raise DimensionMismatch(f"diag of a Vector of size {w.size} where {n} x {n} is expected")
+    return w.diag()
 
 
 def matrix_scalar_forbidden(agg):

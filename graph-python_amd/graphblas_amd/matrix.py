@@ -334,6 +334,12 @@ class Matrix(BaseType):
     def kronecker(self, other, op=None):
         return _kronecker(self, other, op)
 
+    def diag(self, k=0, dtype=None, *, name=None, **opts):
+        """Diagonal ``k`` as a new Vector (GxB_Vector_diag; reference core/matrix.py:735-754)."""
+        from .ss import diag
+
+        return diag(self, k=k, dtype=dtype, name=name, **opts)
+
     def isequal(self, other, *, check_dtype=False):
         """reference core/matrix.py:357-398"""
         if isinstance(other, TransposedMatrix):
@@ -531,6 +537,13 @@ class TransposedMatrix:
 
     def power(self, n, op=None):
         return self.new().power(n, op)
+
+    def diag(self, k=0, dtype=None, *, name=None, **opts):
+        """Diagonal ``k`` of the transpose: diagonal ``-k`` of the matrix, nothing is transposed
+        (reference core/matrix.py:3677-3679)."""
+        from .ss import _diag_k
+
+        return self._matrix.diag(-_diag_k(k), dtype, name=name, **opts)
 
     def reduce_rowwise(self, op=None):
         return _reduce_rows(self, op, columnwise=False)

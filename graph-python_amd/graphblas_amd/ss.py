@@ -18,6 +18,11 @@ entries of every row are ``C, P = A.ss.sort(">")`` followed by
 ``split`` / ``concat`` are one call of GxB_Matrix_split / GxB_Matrix_concat (csrc/gb_tile.hip)
 whatever the number of tiles; vectors go through the same two entry points as N x 1 objects, as
 in the reference (core/ss/matrix.py:281-381, core/ss/vector.py:185-265, ss/_core.py:73-107).
+
+``diag`` / ``build_diag`` / ``reshape`` / ``flatten`` are one call each of GxB_Matrix_diag,
+GxB_Vector_diag, GxB_Matrix_reshape[Dup] and GxB_Vector_flatten (csrc/gb_reindex.hip): the values
+stay on the device and only their indices change (reference ss/_core.py:24-70,
+core/ss/matrix.py:252-279, 3717-3815, core/ss/vector.py:147-183, 1377-1405).
 """
 import ctypes
 from math import ceil, log2
@@ -326,6 +331,107 @@ _ORDERS = {"rowwise": "rowwise", "row": "rowwise", "rows": "rowwise", "c": "roww
            "columns": "columnwise", "f": "columnwise"}
 
 
+class _NewHandle:
+    """``&C`` of an object the call creates; errors of the call are read from ``exc_arg``."""
+
+    def __init__(self, obj, exc_arg):
+        self.obj = obj
+        self._exc_arg = exc_arg
+
+    @property
+    def _carg(self):
+        return ctypes.byref(self.obj._h)
+
+    @property
+    def name(self):
+        return f"&{self.obj.name}"
+
+
+def _order(order):
+    """"rowwise" or "columnwise" for any alias in ``_ORDERS`` (reference core/ss/matrix.py get_order)."""
+    key = order.lower() if isinstance(order, str) else order
+    if key not in _ORDERS:
+        raise ValueError(f"Bad value for order: {order!r}")
+    return _ORDERS[key]
+
+
+def _expect_type(self, x, types, *, within, argname):
+    """``x`` if its type is one of ``types``, else the reference's TypeError (core/base.py:57-110)."""
+    if not isinstance(types, tuple):
+        types = (types,)
+    if type(x) in types:
+        return x
+    owner = self if isinstance(self, str) else type(self).__name__
+    raise TypeError(f"Bad type for argument `{argname}` in {owner}.{within}(...).\n"
+                    f"    - Expected type: {', '.join(t.__name__ for t in types)}.\n"
+                    f"    - Got: {type(x)}.")
+
+
+def _diag_k(k):
+    """The diagonal ``k`` as an int: an integer or a Scalar that holds one (cast as INT64)."""
+    from .scalar import Scalar
+
+    if isinstance(k, Scalar):
+        k = k.value
+        if k is None:
+            raise TypeError("k must not be an empty Scalar")
+    if isinstance(k, bool) or _integral(k) is None:
+        raise TypeError(f"k must be an integer; got: {type(k)}")
+    return _integral(k)
+
+
+def _diag_size(nrows, ncols, k):
+    """Length of diagonal ``k`` of an nrows x ncols matrix (reference ss/_core.py:64-67)."""
+    if k < 0:
+        return max(0, min(nrows + k, ncols))
+    return max(0, min(ncols - k, nrows))
+
+
+def _reshape_shape(shape, nrows, ncols):
+    """The (nrows, ncols) a reshape of an object of ``shape`` is asked for: ``-1`` for one of them,
+    a tuple as ``nrows``; numpy's own ValueError "cannot reshape array" when the sizes do not fit
+    (reference core/ss/matrix.py:3779-3786: the reshape of a broadcast view, which moves nothing)."""
+    array = np.broadcast_to(False, shape)
+    array = array.reshape(nrows) if ncols is None else array.reshape(nrows, ncols)
+    if array.ndim != 2:
+        raise ValueError(f"Shape tuple must be of length 2, not {array.ndim}")
+    return int(array.shape[0]), int(array.shape[1])
+
+
+def _reshape_dup(parent, shape, nrows, ncols, order, name):
+    """GxB_Matrix_reshapeDup of a Matrix, or of a Vector as size x 1, into a new Matrix."""
+    from .base import _autoname
+    from .matrix import Matrix
+
+    columnwise = _order(order) == "columnwise"
+    nrows, ncols = _reshape_shape(shape, nrows, ncols)
+    C = Matrix.__new__(Matrix)
+    C.dtype, C.name = parent.dtype, _autoname("M") if name is None else name
+    C._h = ctypes.c_void_p()
+    C._nrows, C._ncols = nrows, ncols
+    call("GxB_Matrix_reshapeDup", [_NewHandle(C, parent), parent, columnwise, nrows, ncols, None])
+    return C
+
+
+def diag(x, k=0, dtype=None, *, name=None, **opts):
+    """GxB_Matrix_diag / GxB_Vector_diag into a new object (reference ss/_core.py:24-70): the
+    diagonal Matrix of a Vector, or diagonal ``k`` of a Matrix or TransposedMatrix as a Vector."""
+    from .matrix import Matrix, TransposedMatrix
+    from .vector import Vector
+
+    x = _expect_type("graphblas.ss", x, (Matrix, TransposedMatrix, Vector), within="diag", argname="x")
+    k = _diag_k(k)
+    descriptor_lookup(**_sort_opts(opts))  # accepted as in the reference, and unused
+    dtype = x.dtype if dtype is None else lookup_dtype(dtype)
+    if type(x) is Vector:
+        size = x._size + abs(k)
+        rv = Matrix(dtype, size, size, name=name)
+    else:
+        rv = Vector(dtype, _diag_size(x._nrows, x._ncols, k), name=name)
+    rv.ss.build_diag(x, k)
+    return rv
+
+
 def _sort_op(parent, op):
     """The typed BinaryOp of a sort (reference core/ss/matrix.py:4029-4033): a Monoid gives its
     binary operator; whether it is an order is the library's decision."""
@@ -392,17 +498,36 @@ class VectorSS:
         rows, m, n, _ = _concat_tiles(tiles, is_matrix=False)
         _concat_into(self._parent, rows, m, n)
 
+    def build_diag(self, matrix, k=0, **opts):
+        """GxB_Vector_diag (reference core/ss/vector.py:147-183): diagonal ``k`` of a Matrix or
+        TransposedMatrix into this Vector, whose old contents are discarded.  ``A.T`` is read as
+        ``A`` with ``-k``: nothing is transposed."""
+        from .matrix import Matrix, TransposedMatrix
+
+        matrix = _expect_type(self._parent, matrix, (Matrix, TransposedMatrix), within="ss.build_diag",
+                              argname="matrix")
+        k = _diag_k(k)
+        desc = descriptor_lookup(**_sort_opts(opts))
+        if type(matrix) is TransposedMatrix:
+            k = -k
+            matrix = matrix._matrix
+        call("GxB_Vector_diag", [self._parent, matrix, k, desc])
+
+    def reshape(self, nrows, ncols=None, order="rowwise", *, name=None):
+        """The Vector as a Matrix of the given shape (reference core/ss/vector.py:1377-1405):
+        GxB_Matrix_reshapeDup of the vector as size x 1, from the bitmap straight to CSR."""
+        parent = self._parent
+        return _reshape_dup(parent, (parent._size, 1), nrows, ncols, order, name)
+
+
 class MatrixSS:
     def __init__(self, parent):
         self._parent = parent
 
     def scan(self, op=None, order="rowwise", *, name=None):
         """Prefix scan along rows (default) or columns (reference core/ss/matrix.py:3701-3715)."""
-        key = order.lower() if isinstance(order, str) else order
-        if key not in _ORDERS:
-            raise ValueError(f"Bad value for order: {order!r}")
         parent = self._parent
-        if _ORDERS[key] == "columnwise":
+        if _order(order) == "columnwise":
             parent = parent.T
         return prefix_scan(parent, _op.monoid.plus if op is None else op, name=name)
 
@@ -413,12 +538,10 @@ class MatrixSS:
         shape, an output that was not requested is ``None``."""
         from .matrix import Matrix
 
-        key = order.lower() if isinstance(order, str) else order
-        if key not in _ORDERS:
-            raise ValueError(f"Bad value for order: {order!r}")
+        columnwise = _order(order) == "columnwise"
         parent = self._parent
         op = _sort_op(parent, op)
-        desc = descriptor_lookup(transpose_first=_ORDERS[key] == "columnwise", **_sort_opts(opts))
+        desc = descriptor_lookup(transpose_first=columnwise, **_sort_opts(opts))
         if not values and not permutation:
             return None, None
         C = Matrix(parent.dtype, parent.nrows, parent.ncols, name="Values") if values else None
@@ -454,3 +577,36 @@ class MatrixSS:
         discarded; Vectors count as N x 1 (reference core/ss/matrix.py:363-381)."""
         rows, m, n, _ = _concat_tiles(tiles, is_matrix=True)
         _concat_into(self._parent, rows, m, n)
+
+    def build_diag(self, vector, k=0, **opts):
+        """GxB_Matrix_diag (reference core/ss/matrix.py:252-279): the diagonal matrix of
+        ``vector`` on diagonal ``k`` into this Matrix, whose old contents are discarded."""
+        from .vector import Vector
+
+        vector = _expect_type(self._parent, vector, Vector, within="ss.build_diag", argname="vector")
+        k = _diag_k(k)
+        call("GxB_Matrix_diag", [self._parent, vector, k, descriptor_lookup(**_sort_opts(opts))])
+
+    def reshape(self, nrows, ncols=None, order="rowwise", *, inplace=False, name=None):
+        """GxB_Matrix_reshape / GxB_Matrix_reshapeDup (reference core/ss/matrix.py:3742-3815): the
+        Matrix with a new shape of as many positions, filled in row-major ("rowwise") or
+        column-major order.  One dimension may be ``-1``; ``nrows`` may be the shape tuple.
+        ``inplace=True`` reshapes this Matrix (row-major: its values do not move) and returns None."""
+        parent = self._parent
+        if not inplace:
+            return _reshape_dup(parent, parent.shape, nrows, ncols, order, name)
+        columnwise = _order(order) == "columnwise"
+        nrows, ncols = _reshape_shape(parent.shape, nrows, ncols)
+        call("GxB_Matrix_reshape", [parent, columnwise, nrows, ncols, None])
+        parent._nrows, parent._ncols = nrows, ncols
+
+    def flatten(self, order="rowwise", *, name=None):
+        """The Matrix as a Vector of nrows * ncols positions, row-major or column-major (reference
+        core/ss/matrix.py:3717-3740): one call of GxB_Vector_flatten."""
+        from .vector import Vector
+
+        parent = self._parent
+        columnwise = _order(order) == "columnwise"
+        w = Vector(parent.dtype, parent._nrows * parent._ncols, name=name)
+        call("GxB_Vector_flatten", [w, parent, columnwise, None])
+        return w

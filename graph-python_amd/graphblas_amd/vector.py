@@ -150,6 +150,20 @@ class Vector(BaseType):
                 w(mask=mask) << self
         return w
 
+    def diag(self, k=0, *, name=None):
+        """The (size + |k|)-square Matrix with this Vector on diagonal ``k`` (GrB_Matrix_diag;
+        reference core/vector.py:620-642)."""
+        from .ss import _diag_k, _NewHandle
+
+        k = _diag_k(k)
+        n = self._size + abs(k)
+        C = Matrix.__new__(Matrix)
+        C.dtype, C.name = self.dtype, _autoname("M") if name is None else name
+        C._h = ctypes.c_void_p()
+        C._nrows, C._ncols = n, n
+        call("GrB_Matrix_diag", [_NewHandle(C, self), self, k])
+        return C
+
     def clear(self):
         call("GrB_Vector_clear", [self])
 

@@ -389,6 +389,31 @@ GrB_Info GxB_Matrix_concat(GrB_Matrix C, const GrB_Matrix *Tiles, const GrB_Inde
 GrB_Info GxB_Matrix_split(GrB_Matrix *Tiles, const GrB_Index m, const GrB_Index n,
                           const GrB_Index *Tile_nrows, const GrB_Index *Tile_ncols, const GrB_Matrix A,
                           const GrB_Descriptor desc);
+/* diag / reshape / flatten (reference core/vector.py:620-642, core/matrix.py:735-754,
+ * core/ss/matrix.py:252-279, 3717-3815, core/ss/vector.py:147-183, 1377-1405): every stored value
+ * is kept, only the index it sits at changes; no mask, no accumulator, the output's old contents
+ * are discarded, values are cast to the output's type, iso stays iso.
+ * Matrix_diag: v(p) lands at (p + max(-k, 0), p + max(k, 0)) of an n x n matrix, n = size + |k|;
+ * the GrB form creates C with v's type, the GxB form fills an existing n x n C (else
+ * GrB_DIMENSION_MISMATCH).  Vector_diag: v(p) = A(p + max(-k, 0), p + max(k, 0)); any k is legal,
+ * v's size must be the diagonal's length (k >= 0: max(0, min(ncols - k, nrows)), k < 0:
+ * max(0, min(nrows + k, ncols))); INP0 transposed reads A' without building it.
+ * reshape (in place) / reshapeDup (into a new matrix): nrows_new * ncols_new must equal
+ * nrows * ncols (GrB_DIMENSION_MISMATCH, compared without overflow), ncols_new >= 2^31 is
+ * GrB_OUT_OF_MEMORY as in GrB_Matrix_new, and a failed call leaves its object as it was.  Entry
+ * (i, j) moves to divmod(i * ncols + j, ncols_new), or with by_col to (lin % nrows_new,
+ * lin / nrows_new), lin = i + j * nrows; the in-place row-major form keeps the value array.  A
+ * vector handle as A of reshapeDup counts as size x 1.
+ * Vector_flatten (this library's own; a vector is a bitmap, not an n x 1 matrix): w(lin) = A(i, j)
+ * in the same two orders, w's size must be nrows * ncols. */
+GrB_Info GrB_Matrix_diag(GrB_Matrix *C, const GrB_Vector v, int64_t k);
+GrB_Info GxB_Matrix_diag(GrB_Matrix C, const GrB_Vector v, int64_t k, const GrB_Descriptor desc);
+GrB_Info GxB_Vector_diag(GrB_Vector v, const GrB_Matrix A, int64_t k, const GrB_Descriptor desc);
+GrB_Info GxB_Matrix_reshape(GrB_Matrix C, bool by_col, GrB_Index nrows_new, GrB_Index ncols_new,
+                            const GrB_Descriptor desc);
+GrB_Info GxB_Matrix_reshapeDup(GrB_Matrix *C, GrB_Matrix A, bool by_col, GrB_Index nrows_new,
+                               GrB_Index ncols_new, const GrB_Descriptor desc);
+GrB_Info GxB_Vector_flatten(GrB_Vector w, const GrB_Matrix A, bool by_col, const GrB_Descriptor desc);
 
 /* ---------------------------------------------------------------- the hot path */
 /* C<Mask> = C accum (A' (+).(x) B')      replaces SuiteSparse GrB_mxm */
@@ -577,7 +602,8 @@ GrB_Info GxB_MatrixMarket_free(void *p);
  * "stat_union_both" / "stat_union_a_only" / "stat_union_b_only" (entries of T the last
  * eWiseUnion computed from both operands, from A' and beta, from alpha and B'),
  * "stat_concat_bitmap" / "stat_split_bitmap" (1 when the last concat / split moved bitmaps, 0
- * when it built CSR), "stat_concat_iso" (1 when the last concat's result was iso), the read-only counters "stat_bfs_spec_adopted" / "stat_bfs_spec_rollbacks" (BFS level
+ * when it built CSR), "stat_concat_iso" (1 when the last concat's result was iso),
+ * "stat_reshape_div64" (1 when the last reshape divided in 64 bits: 2^32 or more positions), the read-only counters "stat_bfs_spec_adopted" / "stat_bfs_spec_rollbacks" (BFS level
  * speculation) and "stat_nvals_copy" (vector counts read by a device copy
  * instead of the producing kernel's host mailbox). */
 GrB_Info GxB_Global_set_int(const char *key, int64_t value);
