@@ -176,8 +176,8 @@ static int64_t *upload_list(const gb_index_list &L, gb_scratch &s) {
     return d;
 }
 
-// T = V(I, J) for a CSR view V
-static void extract_csr(gb_mat_result &T, const gb_csr_view &v, const gb_index_list &LI, const gb_index_list &LJ) {
+// T = V(I, J) for a CSR view V (also the first step of a subassign, gb_subassign.hip)
+void gb_extract_csr(gb_mat_result &T, const gb_csr_view &v, const gb_index_list &LI, const gb_index_list &LJ) {
     gb_scratch s;
     const int64_t ni = LI.n, nj = LJ.n;
     GB_REQUIRE(ni < (1LL << 31) && nj < (1LL << 31), GrB_NOT_IMPLEMENTED, "extract of more than 2^31 rows/columns");
@@ -246,6 +246,54 @@ static void extract_csr(gb_mat_result &T, const gb_csr_view &v, const gb_index_l
     }
 }
 
+// T(k) = V(j, I[k]) (all: k itself) as a bitmap of LI.n positions, counted
+void gb_extract_line(gb_vec_result &T, const gb_csr_view &v, int64_t j, const gb_index_list &LI) {
+    gb_scratch s;
+    const int64_t *dI = upload_list(LI, s);
+    int64_t e[2];
+    gb_copy_d2h(e, v.rowptr + j, 2 * sizeof(int64_t));
+    T = gb_new_vec_result(LI.n, v.tcode, v.iso);
+    const size_t ts = gb_type_size(v.tcode);
+    if (v.iso) gb_copy_d2d(T.dense, v.vals, ts);
+    if (LI.n) {
+        gb_with_size(ts, [&](auto z) {
+            using V = decltype(z);
+            hipLaunchKernelGGL((k_ext_col<V>), dim3(gb_grid(LI.n, EXT_BLOCK, 16384)), dim3(EXT_BLOCK), 0,
+                               gb_stream(), LI.n, dI, v.colidx, e[0], e[1], (const V *)v.vals, T.bits,
+                               v.iso ? nullptr : (V *)T.dense);
+        }, true);  // any other size: not implemented
+        GB_LAUNCH_CHECK();
+    }
+    gb_bitmap_count(T.bits, LI.n, T.d_nvals);
+}
+
+// T(k) = u(I[k]) as a bitmap of LI.n positions, counted
+void gb_extract_vec(gb_vec_result &T, const gb_bitmap_view &uv, const gb_index_list &LI) {
+    gb_scratch s;
+    std::vector<int64_t> ident;
+    const int64_t *dI = upload_list(LI, s);
+    if (LI.all && LI.n) {
+        int64_t *d = s.get<int64_t>(LI.n);
+        ident.resize(LI.n);
+        for (int64_t k = 0; k < LI.n; k++) ident[k] = k;
+        gb_copy_h2d(d, ident.data(), LI.n * sizeof(int64_t));
+        dI = d;
+    }
+    T = gb_new_vec_result(LI.n, uv.tcode, uv.iso);
+    const size_t ts = gb_type_size(uv.tcode);
+    if (uv.iso) gb_copy_d2d(T.dense, uv.vals, ts);
+    if (LI.n) {
+        gb_with_size(ts, [&](auto z) {
+            using V = decltype(z);
+            hipLaunchKernelGGL((k_ext_vec<V>), dim3(gb_grid(LI.n, EXT_BLOCK, 16384)), dim3(EXT_BLOCK), 0,
+                               gb_stream(), LI.n, dI, uv.bits, (const V *)uv.vals, T.bits,
+                               uv.iso ? nullptr : (V *)T.dense);
+        }, true);  // any other size: not implemented
+        GB_LAUNCH_CHECK();
+    }
+    gb_bitmap_count(T.bits, LI.n, T.d_nvals);
+}
+
 extern "C" {
 
 GrB_Info GrB_Matrix_extract(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum, const GrB_Matrix A,
@@ -265,7 +313,7 @@ GrB_Info GrB_Matrix_extract(GrB_Matrix C, const GrB_Matrix Mask, const GrB_Binar
         GB_REQUIRE(Co->nrows == LI.n && cc == LJ.n, GrB_DIMENSION_MISMATCH,
                    "output dimensions do not match the index lists");
         gb_mat_result T;
-        extract_csr(T, v, LI, LJ);
+        gb_extract_csr(T, v, LI, LJ);
         gb_writeback_matrix(Co, T, Mo, d, accum);
     });
 }
@@ -284,23 +332,8 @@ GrB_Info GrB_Col_extract(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp
         gb_index_list LI;
         gb_expand_indices(LI, I, ni, v.ncols);
         GB_REQUIRE(W->nrows == LI.n, GrB_DIMENSION_MISMATCH, "output size does not match the index list");
-        gb_scratch s;
-        const int64_t *dI = upload_list(LI, s);
-        int64_t e[2];
-        gb_copy_d2h(e, v.rowptr + j, 2 * sizeof(int64_t));
-        gb_vec_result T = gb_new_vec_result(LI.n, v.tcode, v.iso);
-        const size_t ts = gb_type_size(v.tcode);
-        if (v.iso) gb_copy_d2d(T.dense, v.vals, ts);
-        if (LI.n) {
-            gb_with_size(ts, [&](auto z) {
-                using V = decltype(z);
-                hipLaunchKernelGGL((k_ext_col<V>), dim3(gb_grid(LI.n, EXT_BLOCK, 16384)), dim3(EXT_BLOCK), 0,
-                                   gb_stream(), LI.n, dI, v.colidx, e[0], e[1], (const V *)v.vals, T.bits,
-                                   v.iso ? nullptr : (V *)T.dense);
-            }, true);  // any other size: not implemented
-            GB_LAUNCH_CHECK();
-        }
-        gb_bitmap_count(T.bits, LI.n, T.d_nvals);
+        gb_vec_result T;
+        gb_extract_line(T, v, (int64_t)j, LI);
         gb_writeback_vector(W, T, Mo, d, accum, false);
     });
 }
@@ -316,29 +349,8 @@ GrB_Info GrB_Vector_extract(GrB_Vector w, const GrB_Vector mask, const GrB_Binar
         gb_index_list LI;
         gb_expand_indices(LI, I, ni, uv.n);
         GB_REQUIRE(W->nrows == LI.n, GrB_DIMENSION_MISMATCH, "output size does not match the index list");
-        gb_scratch s;
-        std::vector<int64_t> ident;
-        const int64_t *dI = upload_list(LI, s);
-        if (LI.all && LI.n) {
-            int64_t *d = s.get<int64_t>(LI.n);
-            ident.resize(LI.n);
-            for (int64_t k = 0; k < LI.n; k++) ident[k] = k;
-            gb_copy_h2d(d, ident.data(), LI.n * sizeof(int64_t));
-            dI = d;
-        }
-        gb_vec_result T = gb_new_vec_result(LI.n, uv.tcode, uv.iso);
-        const size_t ts = gb_type_size(uv.tcode);
-        if (uv.iso) gb_copy_d2d(T.dense, uv.vals, ts);
-        if (LI.n) {
-            gb_with_size(ts, [&](auto z) {
-                using V = decltype(z);
-                hipLaunchKernelGGL((k_ext_vec<V>), dim3(gb_grid(LI.n, EXT_BLOCK, 16384)), dim3(EXT_BLOCK), 0,
-                                   gb_stream(), LI.n, dI, uv.bits, (const V *)uv.vals, T.bits,
-                                   uv.iso ? nullptr : (V *)T.dense);
-            }, true);  // any other size: not implemented
-            GB_LAUNCH_CHECK();
-        }
-        gb_bitmap_count(T.bits, LI.n, T.d_nvals);
+        gb_vec_result T;
+        gb_extract_vec(T, uv, LI);
         gb_writeback_vector(W, T, Mo, d, accum, false);
     });
 }

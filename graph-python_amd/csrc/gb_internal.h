@@ -472,6 +472,15 @@ struct gb_index_list {
     std::vector<int64_t> idx;  // explicit indices (all == false)
 };
 void gb_expand_indices(gb_index_list &L, const GrB_Index *I, GrB_Index ni, int64_t n);
+struct gb_mat_result;
+struct gb_vec_result;
+struct gb_csr_view;
+struct gb_bitmap_view;
+// the gathers of the extract family (gb_extract.hip), which a subassign (gb_subassign.hip) starts
+// with: T = V(I, J); T(k) = V(j, I[k]); T(k) = u(I[k]).  The vector results are counted.
+void gb_extract_csr(gb_mat_result &T, const gb_csr_view &v, const gb_index_list &LI, const gb_index_list &LJ);
+void gb_extract_line(gb_vec_result &T, const gb_csr_view &v, int64_t j, const gb_index_list &LI);
+void gb_extract_vec(gb_vec_result &T, const gb_bitmap_view &uv, const gb_index_list &LI);
 
 // ------------------------------------------------------------------ ops
 struct gb_desc {

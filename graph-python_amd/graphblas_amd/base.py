@@ -547,3 +547,41 @@ class BaseExpression:
 
     def _new_scalar(self):
         return self.new()
+
+    # ---- C[I, J] as a target.  Matrix / Vector __getitem__ record (parent, keys) on the extract
+    # expression they return; `C[I, J] << A` assigns, `C[I, J](M, accum, replace) << A` is the
+    # subassign with a mask of the region's shape (reference core/expr.py:237-396, AmbiguousAssignOrExtract)
+    _target = None
+
+    def _require_target(self):
+        if self._target is None:
+            raise TypeError(f"{type(self).__name__} of {self.method_name} is not an assignment target")
+        return self._target
+
+    def __call__(self, *optional_mask_accum_replace, mask=None, accum=None, replace=False, **opts):
+        parent, keys = self._require_target()
+        upd = parent(*optional_mask_accum_replace, mask=mask, accum=accum, replace=replace, **opts)
+        return _SubUpdater(parent, keys, upd.mask, upd.accum, upd.replace)
+
+    def __lshift__(self, value):
+        parent, keys = self._require_target()
+        parent._assign(keys, value, None, None, False)
+
+    def update(self, value):
+        parent, keys = self._require_target()
+        parent._assign(keys, value, None, None, False)
+
+
+class _SubUpdater:
+    """C[I, J](mask, accum, replace): the output parameters of a subassign."""
+
+    __slots__ = "parent", "keys", "mask", "accum", "replace"
+
+    def __init__(self, parent, keys, mask, accum, replace):
+        self.parent, self.keys, self.mask, self.accum, self.replace = parent, keys, mask, accum, replace
+
+    def __lshift__(self, value):
+        self.parent._subassign(self.keys, value, self.mask, self.accum, self.replace)
+
+    def update(self, value):
+        self.parent._subassign(self.keys, value, self.mask, self.accum, self.replace)

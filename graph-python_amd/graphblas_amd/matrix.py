@@ -252,16 +252,22 @@ class Matrix(BaseType):
         from .vector import VectorExpression
 
         if rk == "scalar":
-            return VectorExpression("extract", "GrB_Col_extract", [self, cc, cn, rc], at=True, dtype=self.dtype,
+            expr = VectorExpression("extract", "GrB_Col_extract", [self, cc, cn, rc], at=True, dtype=self.dtype,
                                     size=cn)
-        if ck == "scalar":
-            return VectorExpression("extract", "GrB_Col_extract", [self, rc, rn, cc], dtype=self.dtype, size=rn)
-        return MatrixExpression("extract", "GrB_Matrix_extract", [self, rc, rn, cc, cn], dtype=self.dtype,
-                                nrows=rn, ncols=cn)
+        elif ck == "scalar":
+            expr = VectorExpression("extract", "GrB_Col_extract", [self, rc, rn, cc], dtype=self.dtype, size=rn)
+        else:
+            expr = MatrixExpression("extract", "GrB_Matrix_extract", [self, rc, rn, cc, cn], dtype=self.dtype,
+                                    nrows=rn, ncols=cn)
+        expr._target = (self, keys)  # C[I, J] << A and C[I, J](M) << A (BaseExpression)
+        return expr
 
     def __setitem__(self, keys, value):
-        if keys is Ellipsis or (isinstance(keys, tuple) and all(k == slice(None) for k in keys)):
+        if keys is Ellipsis or (isinstance(keys, tuple) and all(_is_full_slice(k) for k in keys)):
             self._assign(Ellipsis, value, None, None, False)
+            return
+        if not (isinstance(keys, tuple) and len(keys) == 2 and all(_is_int(k) for k in keys)):
+            self._assign(keys, value, None, None, False)
             return
         i, j = _scalar_keys(keys, 2)
         from .scalar import Scalar
@@ -278,27 +284,147 @@ class Matrix(BaseType):
         call("GrB_Matrix_removeElement", [self, i, j])
 
     def _assign(self, keys, value, mask, accum, replace):
+        """C(mask, accum, replace)[keys] << value: which call each form becomes follows the reference's
+        _prep_for_assign (core/matrix.py:2905-3316).  Without a mask, assign and subassign are one operation,
+        so C[I, J] << A is GxB_Matrix_subassign; a mask of C's shape with index lists needs
+        GrB_Matrix_assign with lists, which the library does not implement."""
         from .scalar import Scalar
+        from .vector import Vector
 
-        if keys not in (Ellipsis,) and not (isinstance(keys, tuple) and all(k == slice(None) for k in keys)) \
-                and keys != slice(None):
-            raise NotImplementedError("Matrix assign supports whole-matrix (A[:, :]) targets")
-        desc = descriptor_lookup(mask_complement=mask.complement if mask is not None else False,
-                                 mask_structure=mask.structure if mask is not None else False,
-                                 output_replace=replace)
-        if isinstance(value, TransposedMatrix):
-            desc = descriptor_lookup(mask_complement=mask.complement if mask is not None else False,
-                                     mask_structure=mask.structure if mask is not None else False,
-                                     output_replace=replace, transpose_first=True)
-            value = value._matrix
-        if isinstance(value, Matrix):
-            call("GrB_Matrix_assign", [self, mask, accum, value, lib.GrB_ALL, self._nrows, lib.GrB_ALL,
-                                       self._ncols, desc])
+        if keys is Ellipsis or (isinstance(keys, tuple) and all(_is_full_slice(k) for k in keys)) \
+                or _is_full_slice(keys):
+            desc = _mask_desc(mask, replace, isinstance(value, TransposedMatrix))
+            if isinstance(value, TransposedMatrix):
+                value = value._matrix
+            if isinstance(value, Matrix):
+                call("GrB_Matrix_assign", [self, mask, accum, value, lib.GrB_ALL, self._nrows, lib.GrB_ALL,
+                                           self._ncols, desc])
+                return
+            if isinstance(value, Scalar):
+                value = value.value
+            call(f"GrB_Matrix_assign_{self.dtype.name}",
+                 [self, mask, accum, value, lib.GrB_ALL, self._nrows, lib.GrB_ALL, self._ncols, desc])
+            return
+        (rk, rc, rn), (ck, cc, cn) = self._region(keys)
+        vmask = mask is not None and mask.parent.ndim == 1
+        if isinstance(value, Vector):
+            if rk == ck:
+                _bad_value(value, "Scalar" if rk == "scalar" else "Scalar, Matrix, TransposedMatrix")
+            if mask is not None and not vmask:  # C(M)[i, J] << v
+                self._matrix_mask_with_lists(mask)
+            n = cn if rk == "scalar" else rn
+            if value._size != n:
+                raise DimensionMismatch(f"value of size {value._size} does not match the {n} selected positions")
+            line = self._ncols if rk == "scalar" else self._nrows
+            if mask is not None and mask.parent._size != line:  # the mask of an assign spans the whole row / column
+                raise DimensionMismatch(f"mask of size {mask.parent._size} does not match the "
+                                        f"{'row' if rk == 'scalar' else 'column'} of size {line}")
+            desc = _mask_desc(mask, replace)
+            if rk == "scalar":
+                call("GrB_Row_assign", [self, mask, accum, value, rc, cc, cn, desc])
+            else:
+                call("GrB_Col_assign", [self, mask, accum, value, rc, rn, cc, desc])
+            return
+        if isinstance(value, (Matrix, TransposedMatrix)):
+            if rk == "scalar" or ck == "scalar":
+                _bad_value(value, "Scalar" if rk == ck else "Scalar, Vector")
+            if vmask:
+                raise TypeError("Unable to use Vector mask on Matrix assignment to a Matrix")
+            if mask is not None:  # C(M)[I, J] << A
+                self._matrix_mask_with_lists(mask)
+            if value.shape != (rn, cn):
+                raise DimensionMismatch(f"value of shape {value.shape} does not match the region {(rn, cn)}")
+            desc = _mask_desc(None, False, isinstance(value, TransposedMatrix))
+            if isinstance(value, TransposedMatrix):
+                value = value._matrix
+            call("GxB_Matrix_subassign", [self, None, accum, value, rc, rn, cc, cn, desc])
+            return
+        # a scalar
+        if vmask:
+            if rk == ck:
+                raise TypeError("Unable to use Vector mask on single element assignment to a Matrix"
+                                if rk == "scalar" else "Unable to use Vector mask on Matrix assignment to a Matrix")
+            expanded = self._expand_scalar(value, cn if rk == "scalar" else rn)
+            self._assign(keys, expanded, mask, accum, replace)
             return
         if isinstance(value, Scalar):
             value = value.value
-        call(f"GrB_Matrix_assign_{self.dtype.name}",
-             [self, mask, accum, value, lib.GrB_ALL, self._nrows, lib.GrB_ALL, self._ncols, desc])
+        if rk == "scalar":
+            rc, rn = _CArray(np.array([rc], np.uint64), "I"), 1
+        if ck == "scalar":
+            cc, cn = _CArray(np.array([cc], np.uint64), "J"), 1
+        call(f"GrB_Matrix_assign_{self.dtype.name}", [self, mask, accum, value, rc, rn, cc, cn,
+                                                      _mask_desc(mask, replace)])
+
+    def _subassign(self, keys, value, mask, accum, replace):
+        """C[keys](mask, accum, replace) << value: the mask has the region's shape (GxB_*_subassign)."""
+        from .scalar import Scalar
+        from .vector import Vector
+
+        if mask is None:  # C[I, J](accum=op) << A: assign and subassign coincide
+            self._assign(keys, value, None, accum, False)
+            return
+        if keys is Ellipsis or _is_full_slice(keys):
+            keys = (slice(None), slice(None))
+        (rk, rc, rn), (ck, cc, cn) = self._region(keys)
+        vmask = mask.parent.ndim == 1
+        if rk == "scalar" and ck == "scalar":
+            if vmask:
+                raise TypeError("Unable to use Vector mask on single element assignment to a Matrix")
+            raise TypeError("Single element assign does not accept a submask")
+        desc = _mask_desc(mask, replace, isinstance(value, TransposedMatrix))
+        if rk == "scalar" or ck == "scalar":
+            if isinstance(value, (Matrix, TransposedMatrix)):
+                _bad_value(value, "Scalar, Vector")
+            if not vmask:
+                raise TypeError("Indices for subassign imply Vector submask, but got Matrix mask instead")
+            n = cn if rk == "scalar" else rn
+            if not isinstance(value, Vector):  # the scalar as a value vector of the mask's size
+                value = self._expand_scalar(value, mask.parent._size)
+            if value._size != n or mask.parent._size != n:
+                raise DimensionMismatch(f"value of size {value._size} and mask of size {mask.parent._size} "
+                                        f"must match the {n} selected positions")
+            if rk == "scalar":
+                call("GxB_Row_subassign", [self, mask, accum, value, rc, cc, cn, desc])
+            else:
+                call("GxB_Col_subassign", [self, mask, accum, value, rc, rn, cc, desc])
+            return
+        if isinstance(value, Vector):
+            _bad_value(value, "Scalar, Matrix, TransposedMatrix")
+        if vmask:
+            raise TypeError("Unable to use Vector mask on Matrix assignment to a Matrix")
+        if mask.parent.shape != (rn, cn):
+            raise DimensionMismatch(f"mask of shape {mask.parent.shape} does not match the region {(rn, cn)}")
+        if isinstance(value, (Matrix, TransposedMatrix)):
+            if value.shape != (rn, cn):
+                raise DimensionMismatch(f"value of shape {value.shape} does not match the region {(rn, cn)}")
+            if isinstance(value, TransposedMatrix):
+                value = value._matrix
+            call("GxB_Matrix_subassign", [self, mask, accum, value, rc, rn, cc, cn, desc])
+            return
+        if not isinstance(value, Scalar):
+            value = Scalar.from_value(value, self.dtype)
+        call("GxB_Matrix_subassign_Scalar", [self, mask, accum, value, rc, rn, cc, cn, desc])
+
+    def _region(self, keys):
+        if not isinstance(keys, tuple) or len(keys) != 2:
+            raise TypeError("Matrix indexing requires a (rows, columns) pair")
+        return _axis_index(keys[0], self._nrows), _axis_index(keys[1], self._ncols)
+
+    def _matrix_mask_with_lists(self, mask):
+        if mask.parent.shape != self.shape:
+            raise DimensionMismatch(f"mask of shape {mask.parent.shape} does not match the output {self.shape}")
+        raise NotImplementedError("C(M)[I, J] << A with a Matrix mask of C's shape needs GrB_Matrix_assign with "
+                                  "index lists, which is not implemented; use the submask form C[I, J](M) << A")
+
+    def _expand_scalar(self, value, n):
+        from .scalar import Scalar
+        from .vector import Vector
+
+        dtype = value.dtype if isinstance(value, Scalar) else self.dtype
+        v = Vector(dtype, n, name="v_temp")
+        v[:] = value
+        return v
 
     # ---------------------------------------------------------------- operations
     def mxm(self, other, op=None):
@@ -398,6 +524,25 @@ def _power(updater, A, n, op):
     updater << result
 
 
+def _is_int(k):
+    return isinstance(k, (int, np.integer)) and not isinstance(k, bool)
+
+
+def _is_full_slice(k):
+    return isinstance(k, slice) and k == slice(None)
+
+
+def _mask_desc(mask, replace, transpose_first=False):
+    return descriptor_lookup(mask_complement=mask.complement if mask is not None else False,
+                             mask_structure=mask.structure if mask is not None else False,
+                             output_replace=replace, transpose_first=transpose_first)
+
+
+def _bad_value(value, expected):
+    raise TypeError(f"Bad type for argument `value` in Matrix.__setitem__(...): expected {expected}; "
+                    f"got {type(value).__name__}")
+
+
 def _axis_index(key, size):
     """One axis of an index: ("scalar", i, 1), or ("list", GrB_ALL | _CArray, length).  Slices
     other than ':' become explicit index arrays (the reference's non-SuiteSparse path,
@@ -463,8 +608,30 @@ class _MatrixElement:
     def __lshift__(self, value):
         self.parent[self.i, self.j] = value
 
+    update = __lshift__
+
+    def __call__(self, *args, **kwargs):
+        upd = self.parent(*args, **kwargs)
+        if upd.mask is not None and upd.mask.parent.ndim == 1:
+            return _NoSubmask("Unable to use Vector mask on single element assignment to a Matrix")
+        return _NoSubmask()
+
     def __eq__(self, other):
         return self.value == other
+
+
+class _NoSubmask:
+    """C[i, j](...) or w[i](...): building it is allowed (as in the reference), assigning through it is not"""
+
+    __slots__ = ("message",)
+
+    def __init__(self, message="Single element assign does not accept a submask"):
+        self.message = message
+
+    def __lshift__(self, value):
+        raise TypeError(self.message)
+
+    update = __lshift__
 
 
 class TransposedMatrix:

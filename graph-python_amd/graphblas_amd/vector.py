@@ -180,7 +180,9 @@ class Vector(BaseType):
         kind, idx, n = _axis_index(key, self._size)
         if kind == "scalar":
             return _VectorElement(self, idx)
-        return VectorExpression("extract", "GrB_Vector_extract", [self, idx, n], dtype=self.dtype, size=n)
+        expr = VectorExpression("extract", "GrB_Vector_extract", [self, idx, n], dtype=self.dtype, size=n)
+        expr._target = (self, key)  # w[I] << u and w[I](m) << u (BaseExpression)
+        return expr
 
     def _as_matrix(self):
         """The same object as an n x 1 Matrix (reference core/vector.py:186-205: a
@@ -231,6 +233,35 @@ class Vector(BaseType):
         if isinstance(value, Scalar):
             value = value.value
         call(f"GrB_Vector_assign_{self.dtype.name}", [self, mask, accum, value, idx, ni, desc])
+
+    def _subassign(self, keys, value, mask, accum, replace):
+        """w[I](mask, accum, replace) << value: the mask has len(I) entries (GxB_Vector_subassign[_Scalar])."""
+        from .scalar import Scalar
+
+        if isinstance(keys, (int, np.integer)) and not isinstance(keys, bool):
+            raise TypeError("Single element assign does not accept a submask")
+        if keys is Ellipsis:
+            keys = slice(None)
+        _, idx, ni = _axis_index(keys, self._size)
+        if mask is not None:
+            if mask.parent.ndim != 1:
+                raise TypeError(f"Mask object must be type Vector; got {type(mask.parent)}")
+            if mask.parent._size != ni:
+                raise DimensionMismatch(f"mask of size {mask.parent._size} does not match the {ni} selected "
+                                        "positions")
+        desc = descriptor_lookup(mask_complement=mask.complement if mask is not None else False,
+                                 mask_structure=mask.structure if mask is not None else False, output_replace=replace)
+        if isinstance(value, Vector):
+            if value._size != ni:
+                raise DimensionMismatch(f"value of size {value._size} does not match the {ni} selected positions")
+            call("GxB_Vector_subassign", [self, mask, accum, value, idx, ni, desc])
+            return
+        if isinstance(value, (Matrix, TransposedMatrix)):
+            raise TypeError("Bad type for argument `value` in Vector.__setitem__(...): expected Scalar, Vector; "
+                            f"got {type(value).__name__}")
+        if not isinstance(value, Scalar):
+            value = Scalar.from_value(value, self.dtype)
+        call("GxB_Vector_subassign_Scalar", [self, mask, accum, value, idx, ni, desc])
 
     # ---------------------------------------------------------------- operations
     def vxm(self, other, op=None):
@@ -350,6 +381,13 @@ class _VectorElement:
 
     def __lshift__(self, value):
         self.parent[self.i] = value
+
+    update = __lshift__
+
+    def __call__(self, *args, **kwargs):
+        from .matrix import _NoSubmask
+
+        return _NoSubmask()
 
     def __eq__(self, other):
         return self.value == other

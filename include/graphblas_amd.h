@@ -490,6 +490,36 @@ GrB_Info GrB_Col_extract(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp
 GrB_Info GrB_Vector_extract(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum,
                             const GrB_Vector u, const GrB_Index *I, GrB_Index ni,
                             const GrB_Descriptor desc);
+/* subassign, and assign on one row or column (reference core/matrix.py:2905-3316, core/vector.py
+ * "GxB_Vector_subassign"): the mask of a GxB_*_subassign has the region's shape and nothing
+ * outside I x J changes; GrB_Row_assign / GrB_Col_assign take a mask over the whole row / column,
+ * which replace then reaches also outside J / I.  INP0 transposes A in GxB_Matrix_subassign
+ * only.  An empty GrB_Scalar assigns a region without entries.  A repeated index in I or J is
+ * refused with GrB_INVALID_VALUE (the specification leaves it undefined) and C is not changed. */
+GrB_Info GxB_Matrix_subassign(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum,
+                              const GrB_Matrix A, const GrB_Index *I, GrB_Index ni,
+                              const GrB_Index *J, GrB_Index nj, const GrB_Descriptor desc);
+GrB_Info GxB_Vector_subassign(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum,
+                              const GrB_Vector u, const GrB_Index *I, GrB_Index ni,
+                              const GrB_Descriptor desc);
+GrB_Info GxB_Row_subassign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum,
+                           const GrB_Vector u, GrB_Index i, const GrB_Index *J, GrB_Index nj,
+                           const GrB_Descriptor desc);
+GrB_Info GxB_Col_subassign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum,
+                           const GrB_Vector u, const GrB_Index *I, GrB_Index ni, GrB_Index j,
+                           const GrB_Descriptor desc);
+GrB_Info GrB_Row_assign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum,
+                        const GrB_Vector u, GrB_Index i, const GrB_Index *J, GrB_Index nj,
+                        const GrB_Descriptor desc);
+GrB_Info GrB_Col_assign(GrB_Matrix C, const GrB_Vector mask, const GrB_BinaryOp accum,
+                        const GrB_Vector u, const GrB_Index *I, GrB_Index ni, GrB_Index j,
+                        const GrB_Descriptor desc);
+GrB_Info GxB_Matrix_subassign_Scalar(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum,
+                                     const GrB_Scalar x, const GrB_Index *I, GrB_Index ni,
+                                     const GrB_Index *J, GrB_Index nj, const GrB_Descriptor desc);
+GrB_Info GxB_Vector_subassign_Scalar(GrB_Vector w, const GrB_Vector mask, const GrB_BinaryOp accum,
+                                     const GrB_Scalar x, const GrB_Index *I, GrB_Index ni,
+                                     const GrB_Descriptor desc);
 /* GrB_MODE of the running library (GrB_BLOCKING / GrB_NONBLOCKING) for field GxB_MODE */
 GrB_Info GxB_Global_Option_get_INT32(GxB_Option_Field field, int32_t *value);
 
