@@ -269,6 +269,12 @@ bool gb_stat_get(const char *name, int64_t *v) {
     return true;
 }
 
+std::atomic<int64_t> g_grid_cap{0};
+void gb_grid_clamped(const char *file, int line) {
+    const char *base = strrchr(file, '/');
+    gb_stat_add(("grid_clamped:" + std::string(base ? base + 1 : file) + ":" + std::to_string(line)).c_str(), 1);
+}
+
 int64_t gb_knob(const char *key) {
     if (!g_any_knob.load(std::memory_order_acquire)) return 0;
     std::lock_guard<std::mutex> lk(g_knob_mu);
@@ -507,6 +513,7 @@ GrB_Info GxB_Global_set_int(const char *key, int64_t value) {
     if (!key) return GrB_NULL_POINTER;
     std::lock_guard<std::mutex> lk(g_knob_mu);
     g_knobs[key] = value;
+    if (!strcmp(key, "grid_cap")) g_grid_cap.store(value > 0 ? value : 0, std::memory_order_relaxed);
     g_any_knob.store(true, std::memory_order_release);
     return GrB_SUCCESS;
 }

@@ -1220,7 +1220,7 @@ int64_t gb_dot_two_sided(const gb_csr_view &A, const gb_csr_view &BT, gb_mmask &
                 nhch = gb_read_i64(hcp + sd.ng);
                 gb_stat_add(SWAP ? "dot_hub_chunks_C" : "dot_hub_chunks_R", nhch);
                 if (nhch)
-                    hipLaunchKernelGGL((k_dt_hub_classify<SWAP>), dim3((unsigned)std::min<int64_t>(nhch, 1 << 16)),
+                    hipLaunchKernelGGL((k_dt_hub_classify<SWAP>), dim3(gb_grid(nhch, 1, 1 << 16)),
                                        dim3(DT_BLOCK), 0, gb_stream(), sd, hcp, nhch, hflag, pieces ? hg : nullptr);
                 GB_LAUNCH_CHECK();
             }
@@ -1333,7 +1333,8 @@ int64_t gb_dot_two_sided(const gb_csr_view &A, const gb_csr_view &BT, gb_mmask &
             int32_t *hB = hs.get<int32_t>(nh);
             int64_t *hQ = hs.get<int64_t>(nh);
             if (hubc) {
-                hipLaunchKernelGGL((k_dt_hub_compact<SWAP>), dim3((unsigned)std::min<int64_t>(nhch, 1 << 16)),
+                // huge entries exist only where k_dt_hub_classify ran: nhch > 0
+                hipLaunchKernelGGL((k_dt_hub_compact<SWAP>), dim3(gb_grid(nhch, 1, 1 << 16)),
                                    dim3(DT_BLOCK), 0, gb_stream(), sd, hcp, nhch, hg, pos, hG, hYS, hO, hB, hQ);
             } else {
                 hipLaunchKernelGGL((k_dt_compact<SWAP>), dim3(gw), dim3(DT_BLOCK), 0, gb_stream(), sd, cap, hg, pos,

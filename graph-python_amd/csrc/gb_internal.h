@@ -292,9 +292,21 @@ int64_t gb_knob(const char *key);
 unsigned long long *gb_device_state();
 // blocks of a launch: ceil(items / per_block) clamped to [1, cap].  A launch that counts waves
 // passes per_block = BLOCK / 64.  The caps differ per file and per kernel: they are tuned.
-inline unsigned gb_grid(int64_t items, int64_t per_block, int64_t cap) {
-    const int64_t g = (items + per_block - 1) / per_block;
-    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
+// Test knob "grid_cap" = k > 0 (GxB_Global_set_int) clamps every such grid to k blocks more, so
+// that a small shape runs a kernel's later grid sweeps; each call site at which that clamp bit
+// is counted as stat_grid_clamped:<file>:<line> ("Grid sweeps").  0: neither.
+extern std::atomic<int64_t> g_grid_cap;
+void gb_grid_clamped(const char *file, int line);
+inline unsigned gb_grid(int64_t items, int64_t per_block, int64_t cap, const char *file = __builtin_FILE(),
+                        int line = __builtin_LINE()) {
+    int64_t g = (items + per_block - 1) / per_block;
+    g = g < 1 ? 1 : g > cap ? cap : g;
+    const int64_t k = g_grid_cap.load(std::memory_order_relaxed);
+    if (k > 0 && g > k) {
+        g = k;
+        gb_grid_clamped(file, line);
+    }
+    return (unsigned)g;
 }
 
 // Host-visible mailboxes in pinned coherent memory: a kernel publishes a

@@ -535,7 +535,7 @@ static int32_t *gb_build_chunk_table(const gb_csr_view &v, int64_t thresh, int64
     gb_scratch s;
     int64_t *cnt = s.get<int64_t>(n + 1);
     int64_t *off = s.get<int64_t>(n + 1);
-    const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192));
+    const unsigned g = gb_grid(n, 256, 8192);
     hipLaunchKernelGGL(k_hub_count, dim3(g), dim3(256), 0, gb_stream(), v.rowptr, n, thresh, H, cnt);
     GB_LAUNCH_CHECK();
     gb_exclusive_scan_i64(cnt, off, n);
@@ -571,7 +571,7 @@ void gb_view_hubs(gb_csr_view &v, GB_Obj *A, int orient, int64_t H) {
         gb_scratch s;
         unsigned long long *mx = s.get<unsigned long long>(1);
         gb_memset(mx, 0, sizeof(unsigned long long));
-        const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((v.nrows + 255) / 256, 2048));
+        const unsigned g = gb_grid(v.nrows, 256, 2048);
         hipLaunchKernelGGL(k_row_maxlen, dim3(g), dim3(256), 0, gb_stream(), v.rowptr, v.nrows, mx);
         GB_LAUNCH_CHECK();
         unsigned long long h = 0;
@@ -628,7 +628,7 @@ void gb_view_nonempty(gb_csr_view &v, GB_Obj *A, int orient) {
             gb_scratch s;
             int32_t *pc = s.get<int32_t>(nw);
             int64_t *pre = s.get<int64_t>(nw + 1);
-            const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nw + 3) / 4, 8192));
+            const unsigned g = gb_grid(nw, 4, 8192);  // a wave per word
             hipLaunchKernelGGL(k_rows_nonempty, dim3(g), dim3(256), 0, gb_stream(), v.rowptr, v.nrows, c.rows_ne, pc);
             GB_LAUNCH_CHECK();
             gb_exclusive_scan_i32(pc, 0, pre, nw);
@@ -708,7 +708,7 @@ void gb_view_pullfirst(gb_csr_view &v, GB_Obj *A, int orient, const int64_t *oth
         const int64_t nrec = std::max<int64_t>(1, (int64_t)ne_count);
         c.phead = gb_malloc_n<int32_t>(4 * nrec);
         c.pdeg = gb_malloc_n<uint32_t>(nrec);
-        const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((v.nrows + 3) / 4, 65535));
+        const unsigned g = gb_grid(v.nrows, 4, 65535);  // a wave per row
         hipLaunchKernelGGL(k_pull_head, dim3(g), dim3(256), 0, gb_stream(), v.nrows, v.rowptr, v.colidx,
                            other_rowptr, other_n, c.rows_ne, c.ne_rank, reinterpret_cast<int4 *>(c.phead), c.pdeg);
         GB_LAUNCH_CHECK();
@@ -781,14 +781,14 @@ void gb_spmv(gb_vec_result &T, const gb_csr_view &A, const gb_csr_view *Apush, g
             const bool u_iso_k = u.iso || gb_knob("spmv_timing_no_x_gather") == 1;  // timing experiment only
             int spmv_mode = gb_knob("spmv_words") == 2 ? 1 : 0;  // 0: segmented scan (default), 2: merge path
             if (gb_knob("spmv_nt") == 1) spmv_mode |= 2;
-            const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((units + 3) / 4, 4096));
+            const unsigned grid = gb_grid(units, SPMV_BLOCK / 64, 4096);
             // dense u on a relabelled matrix: the hot columns' values packed first (gb_view_hot);
             // positional multipliers need the true column, so they keep the plain colidx
             const int32_t *ci = A.colidx;
             X *uhot = nullptr;
             if (A.hcolidx && u.full && !u_iso_k && uv && !info.positional && info.reads_values) {
                 uhot = s.get<X>(A.nhot);
-                const unsigned hg = (unsigned)std::max<int64_t>(1, std::min<int64_t>((A.nhot + 255) / 256, 2048));
+                const unsigned hg = gb_grid(A.nhot, 256, 2048);
                 hipLaunchKernelGGL((k_hot_gather<X>), dim3(hg), dim3(256), 0, gb_stream(), (const X *)uv, A.hcols,
                                    A.nhot, uhot);
                 GB_LAUNCH_CHECK();
@@ -803,7 +803,7 @@ void gb_spmv(gb_vec_result &T, const gb_csr_view &A, const gb_csr_view *Apush, g
             });
             GB_LAUNCH_CHECK();
             if (A.nlchunks > 0) {
-                const unsigned fg = (unsigned)std::max<int64_t>(1, std::min<int64_t>((A.nlchunks + 255) / 256, 1024));
+                const unsigned fg = gb_grid(A.nlchunks, 256, 1024);
                 hipLaunchKernelGGL((k_spmv_fold<SRT, Z>), dim3(fg), dim3(256), 0, gb_stream(), srf, A.lchunks,
                                    A.nlchunks, cpart, cfound, T.bits, (Z *)T.dense, (unsigned long long *)T.d_nvals,
                                    gst);
@@ -818,7 +818,7 @@ void gb_spmv(gb_vec_result &T, const gb_csr_view &A, const gb_csr_view *Apush, g
         while (lg < 6 && (1LL << lg) < avg) lg++;
         const int64_t forced = gb_knob("spmv_lg");
         if (forced > 0) lg = (int)(forced - 1);
-        const unsigned grid = (unsigned)std::min<int64_t>((n + SPMV_TILE - 1) / SPMV_TILE, 2048);
+        const unsigned grid = gb_grid(n, SPMV_TILE, 2048);  // n > 0 here
         gb_with_flip(flip, [&](auto fl) {
             hipLaunchKernelGGL((k_spmv_pull<SRT, X, Z, decltype(fl)::value>), dim3(grid), dim3(SPMV_BLOCK), 0,
                                gb_stream(), srf, n, A.rowptr, A.colidx, (const X *)av, A.iso, u.bits, (const X *)uv,

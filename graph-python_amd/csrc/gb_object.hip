@@ -330,10 +330,8 @@ const int64_t *gb_csc_perm(GB_Obj *A) {
     if (!A->t_perm) {
         A->t_perm = gb_malloc_n<int64_t>(A->nvals ? A->nvals : 1);
         if (A->nvals) {
-            int64_t blocks = (A->ncols + 3) / 4;
-            if (blocks > 65535) blocks = 65535;
-            hipLaunchKernelGGL(k_csc_perm, dim3((unsigned)blocks), dim3(256), 0, gb_stream(), A->ncols, A->t_rowptr,
-                               A->t_colidx, A->rowptr, A->colidx, A->t_perm);
+            hipLaunchKernelGGL(k_csc_perm, dim3(gb_grid(A->ncols, 4, 65535)), dim3(256), 0, gb_stream(), A->ncols,
+                               A->t_rowptr, A->t_colidx, A->rowptr, A->colidx, A->t_perm);
             GB_LAUNCH_CHECK();
         }
     }

@@ -31,7 +31,9 @@ template <class It>
 static void scan_chunked(It in, int64_t *out, int64_t n) {
     gb_memset(out, 0, sizeof(int64_t));
     if (n == 0) return;
-    const int64_t CH = (int64_t)1 << 30;
+    // knob scan_chunk (tests): a smaller chunk, so that the carry runs below 2^30 items
+    const int64_t kch = gb_knob("scan_chunk");
+    const int64_t CH = kch > 0 && kch < ((int64_t)1 << 30) ? kch : (int64_t)1 << 30;
     size_t tmp = 0;
     GB_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tmp, in, out + 1, (int)std::min(n, CH), gb_stream()));
     void *t = gb_malloc(tmp);
@@ -145,7 +147,7 @@ static bool scanw(const T *in, int64_t add, int64_t *out, int64_t n) {
     const int64_t nt = (n + SCW_TILE - 1) / SCW_TILE;
     int64_t *ts = gb_malloc_n<int64_t>(nt);
     int64_t *to = gb_malloc_n<int64_t>(nt + 1);
-    const unsigned g = (unsigned)std::min<int64_t>((nt + 3) / 4, 8192);
+    const unsigned g = gb_grid(nt, 4, 8192);  // four wave tiles per block
     hipLaunchKernelGGL(k_scanw_sums<T>, dim3(g), dim3(256), 0, gb_stream(), in, add, n, nt, ts);
     GB_LAUNCH_CHECK();
     scan_chunked(ts, to, nt);
@@ -263,7 +265,7 @@ void gb_exclusive_scan_u8(const uint8_t *in, int64_t *out, int64_t n) {
     const int64_t nt = (n + SC_TILE - 1) / SC_TILE;
     int64_t *ts = gb_malloc_n<int64_t>(nt);
     int64_t *to = gb_malloc_n<int64_t>(nt + 1);
-    const unsigned g = (unsigned)std::min<int64_t>((nt + 3) / 4, 8192);
+    const unsigned g = gb_grid(nt, 4, 8192);  // four wave tiles per block
     hipLaunchKernelGGL(k_scan_u8_sums, dim3(g), dim3(256), 0, gb_stream(), in, n, nt, ts);
     GB_LAUNCH_CHECK();
     gb_exclusive_scan_i64(ts, to, nt);
@@ -512,20 +514,20 @@ template <class W>
 __global__ void k_csr_col_to_bitmap(const int64_t *__restrict__ rowptr, const W *__restrict__ vals,
                                     bool iso, int64_t n, uint64_t *__restrict__ bits,
                                     W *__restrict__ dense) {
-    int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     int64_t nw = (n + 63) >> 6;
-    if (w >= nw) return;
-    uint64_t word = 0;
-    for (int b = 0; b < 64; b++) {
-        int64_t i = (w << 6) + b;
-        if (i >= n) break;
-        int64_t p = rowptr[i];
-        if (rowptr[i + 1] > p) {
-            word |= 1ULL << b;
-            if (dense) dense[i] = iso ? vals[0] : vals[p];
+    GB_GRID_LOOP(w, nw) {
+        uint64_t word = 0;
+        for (int b = 0; b < 64; b++) {
+            int64_t i = (w << 6) + b;
+            if (i >= n) break;
+            int64_t p = rowptr[i];
+            if (rowptr[i + 1] > p) {
+                word |= 1ULL << b;
+                if (dense) dense[i] = iso ? vals[0] : vals[p];
+            }
         }
+        bits[w] = word;
     }
-    bits[w] = word;
 }
 
 void gb_csr_col_to_bitmap(const gb_csr_view &v, size_t tsize, uint64_t **bits, void **dense,

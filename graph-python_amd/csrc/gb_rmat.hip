@@ -129,7 +129,7 @@ extern "C" GrB_Info GxB_Matrix_rmat(GrB_Matrix *A, int scale, int edge_factor, u
             gb_copy_d2h(&hc, cnt, 8);
             const int64_t m = (int64_t)hc;
             int64_t *head = s.get<int64_t>(m + 1), *pos = s.get<int64_t>(m + 1);
-            unsigned grid = (unsigned)std::min<int64_t>(8192, (m + 255) / 256 + 1);
+            unsigned grid = gb_grid(m + 256, 256, 8192);  // one block more than the m keys need
             hipLaunchKernelGGL(k_rmat_heads, dim3(grid), dim3(256), 0, gb_stream(), keys, m, head);
             GB_LAUNCH_CHECK();
             gb_exclusive_scan_i64(head, pos, m);
