@@ -79,7 +79,9 @@ enum { GB_KIND_MATRIX = 0, GB_KIND_VECTOR = 1, GB_KIND_SCALAR = 2 };
 
 // Per-orientation caches of a matrix, attached lazily by the gb_view_* builders and freed
 // together by gb_orient_cache_drop (gb_object.hip), which frees the device pointers and
-// resets every field to the defaults below.
+// resets every field to the defaults below.  Each builder counts its builds (gb_stat_add:
+// stat_hub_tables_built, stat_nonempty_built, ...), and every field is named in the READS table
+// of tests/derived_state_cases.py next to the probe that reads it after a mutation.
 struct gb_orient_cache {
     // hub-chunk table, built by gb_view_hubs (gb_mxv.hip)
     int32_t *hub_tab = nullptr;

@@ -564,6 +564,7 @@ void gb_view_hubs(gb_csr_view &v, GB_Obj *A, int orient, int64_t H) {
     if (A->kind != GB_KIND_MATRIX) return;
     gb_orient_cache &c = A->oc[orient];
     if (!c.hub_tab || c.hub_H != H) {
+        gb_stat_add("hub_tables_built", 1);
         gb_free(c.hub_tab);
         c.hub_tab = gb_build_chunk_table(v, H, H, &c.hub_n);
         c.hub_H = H;
@@ -587,7 +588,10 @@ void gb_view_hubs(gb_csr_view &v, GB_Obj *A, int orient, int64_t H) {
 void gb_view_long_rows(gb_csr_view &v, GB_Obj *A, int orient) {
     if (A->kind != GB_KIND_MATRIX) return;
     gb_orient_cache &c = A->oc[orient];
-    if (!c.long_tab) c.long_tab = gb_build_chunk_table(v, SPMV_LONG, SPMV_CH, &c.long_n);
+    if (!c.long_tab) {
+        gb_stat_add("long_tables_built", 1);
+        c.long_tab = gb_build_chunk_table(v, SPMV_LONG, SPMV_CH, &c.long_n);
+    }
     v.lchunks = c.long_tab;
     v.nlchunks = c.long_n;
 }
@@ -619,6 +623,7 @@ void gb_view_nonempty(gb_csr_view &v, GB_Obj *A, int orient) {
     if (A->kind != GB_KIND_MATRIX) return;
     gb_orient_cache &c = A->oc[orient];
     if (!c.rows_ne) {
+        gb_stat_add("nonempty_built", 1);
         const int64_t nw = gb_words(v.nrows);
         c.rows_ne = gb_malloc_n<uint64_t>(nw);
         c.ne_rank = gb_malloc_n<uint32_t>(nw + 1);
@@ -701,6 +706,7 @@ void gb_view_pullfirst(gb_csr_view &v, GB_Obj *A, int orient, const int64_t *oth
     // the records are found through the non-empty bitmap's ranks: no heads without them
     if (!c.rows_ne || !c.ne_rank || v.nonempty != c.rows_ne || v.ne_rank != c.ne_rank) return;
     if (!c.phead) {
+        gb_stat_add("pull_heads_built", 1);
         // one record per non-empty row: their count is the prefix's last entry (read once per
         // matrix orientation, when the heads are built)
         uint32_t ne_count = 0;

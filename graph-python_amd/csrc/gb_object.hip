@@ -328,6 +328,7 @@ const int64_t *gb_csc_perm(GB_Obj *A) {
     gb_csr_view v;
     gb_get_csc(v, A);
     if (!A->t_perm) {
+        gb_stat_add("csc_perms_built", 1);
         A->t_perm = gb_malloc_n<int64_t>(A->nvals ? A->nvals : 1);
         if (A->nvals) {
             hipLaunchKernelGGL(k_csc_perm, dim3(gb_grid(A->ncols, 4, 65535)), dim3(256), 0, gb_stream(), A->ncols,

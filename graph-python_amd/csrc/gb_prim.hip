@@ -688,6 +688,7 @@ void gb_view_hot(gb_csr_view &v, GB_Obj *A, int orient) {
         // worth it only when x does not fit the L2 anyway and there is enough to gather
         if (knob != 2 && (v.nvals < (1LL << 22) || v.ncols <= 2 * H)) return;
         if (H <= 0 || v.nvals == 0) return;
+        gb_stat_add("hot_relabels_built", 1);
         const int64_t nc = v.ncols;
         gb_scratch s;
         uint32_t *cnt = s.get<uint32_t>(nc), *cnt2 = s.get<uint32_t>(nc);
@@ -776,6 +777,7 @@ void gb_view_narrow(gb_csr_view &v, GB_Obj *A, int orient) {
     const bool uns = code == GBAMD_T_UINT16 || code == GBAMD_T_UINT32 || code == GBAMD_T_UINT64;
     if (!sgn && !uns) return;
     if (!A->oc[orient].nar_done) {
+        gb_stat_add("narrow_built", 1);
         const size_t ts = gb_type_size(code);
         gb_scratch s;
         long long *st = s.get<long long>(3);
