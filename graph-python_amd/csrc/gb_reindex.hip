@@ -4,6 +4,10 @@
 //   GxB_Matrix_reshape / _reshapeDup     reference core/ss/matrix.py:3742-3815, core/ss/vector.py:1377-1405
 //   GxB_Vector_flatten                   reference core/ss/matrix.py:3717-3740 (this backend's own entry point:
 //                                        a vector is a bitmap here, no n x 1 matrix cast gives one)
+//   GxB_{Matrix,Vector}_import_dense     reference core/matrix.py:1457-1518, core/vector.py:894-946
+//   GxB_{Matrix,Vector}_export_dense     reference core/matrix.py:1520-1574, core/vector.py:948-999
+//                                        (this backend's own names: a dense array, host or device,
+//                                        in and out; the layout is stated with the code below)
 // No mask, no accumulator; the output's old contents are discarded.
 //
 // Layout formulas.  A vector is a bitmap with dense values; rank(p) = the entries below position p
@@ -39,6 +43,12 @@
 //                     value stored at lin.  The atomic has no reader (no return value is used),
 //                     serves both orders with one kernel (column-major entries of one word are not
 //                     neighbours in storage) and words shared by two waves need it in any case
+//   k_dense_flags     one lane per position of a dense array, the wave's ballot of "holds an
+//                     entry" is the bitmap word that k_bitmap_csr then reads
+//   k_dense_fill      the fill value over a whole array in 16-byte stores
+//   k_dense_scatter   one lane per entry, the row from gb_chunk_rows, the value stored at
+//                     row * ncols + col.  Positions are unique: no atomics
+//   k_bitmap_dense    one lane per position of a vector: its value or the fill, and its bit as a byte
 #include <algorithm>
 
 #include "gb_dispatch.cuh"
@@ -179,6 +189,114 @@ __global__ __launch_bounds__(RIX_BLOCK) void k_flatten(int64_t nvals, int64_t nr
             const int64_t lin = row[u] * mi + (int64_t)ci[p] * mj;
             atomicOr(&bits[lin >> 6], 1ULL << (lin & 63));
             if (vx) dense[lin] = vx[p];
+        }
+    }
+}
+
+// ------------------------------------------------------------------ dense import / export
+// the run of chunks [g0, g1) of RIX_WPI * 64 items that this thread's wave takes out of n items
+GB_DEV void rix_wave_chunks(int64_t n, int64_t &g0, int64_t &g1) {
+    const int64_t nwaves = ((int64_t)gridDim.x * RIX_BLOCK) >> 6;
+    const int64_t ngroups = (n + RIX_WPI * 64 - 1) / (RIX_WPI * 64);
+    const int64_t per_wave = (ngroups + nwaves - 1) / nwaves;
+    g0 = ((blockIdx.x * (int64_t)RIX_BLOCK + threadIdx.x) >> 6) * per_wave;
+    g1 = min(g0 + per_wave, ngroups);
+}
+
+// bits[p >> 6] bit p & 63 = position p of the dense array holds an entry: its byte of Ab (when
+// given) is not 0 and its value is != m (when has_m).  C: the type `!=` is C's in -- float and
+// double for the float types (NaN != NaN, -0 == 0), the unsigned word for the others.  A wave
+// per 64 positions, its ballot the word: no bit at or past n
+template <class C>
+__global__ __launch_bounds__(RIX_BLOCK) void k_dense_flags(int64_t n, const C *__restrict__ X,
+                                                           const int8_t *__restrict__ Ab, bool has_m, C m,
+                                                           uint64_t *__restrict__ bits) {
+    const int lane = threadIdx.x & 63;
+    int64_t g0, g1;
+    rix_wave_chunks(n, g0, g1);
+    for (int64_t g = g0; g < g1; g++) {
+#pragma unroll
+        for (int u = 0; u < RIX_WPI; u++) {
+            const int64_t w0 = g * (RIX_WPI * 64) + u * 64, p = w0 + lane;
+            if (w0 >= n) break;  // the wave as one
+            bool keep = p < n;
+            if (keep && Ab) keep = Ab[p] != 0;
+            if (keep && has_m) keep = X[p] != m;
+            const unsigned long long word = __ballot(keep);
+            if (lane == 0) bits[w0 >> 6] = word;
+        }
+    }
+}
+
+// x[0 .. n) = val: 16-byte stores between the first and the last 16-byte boundary, the (fewer
+// than 16 / sizeof(W)) elements before and after them by the first wave's lanes
+template <class W>
+__global__ __launch_bounds__(RIX_BLOCK) void k_dense_fill(int64_t n, W *__restrict__ x, W val) {
+    constexpr int64_t PER = 16 / sizeof(W);
+    const int lane = threadIdx.x & 63;
+    const int64_t head = min(n, (int64_t)(((16 - ((uintptr_t)x & 15)) & 15) / sizeof(W)));
+    const int64_t nvec = (n - head) / PER, tail0 = head + nvec * PER;
+    uint64_t rep = (uint64_t)val;
+#pragma unroll
+    for (int s = 8 * sizeof(W); s < 64; s *= 2) rep |= rep << s;
+    const ulonglong2 pat = make_ulonglong2(rep, rep);
+    ulonglong2 *__restrict__ xv = (ulonglong2 *)(x + head);
+    int64_t g0, g1;
+    rix_wave_chunks(nvec, g0, g1);
+    for (int64_t g = g0; g < g1; g++) {
+#pragma unroll
+        for (int u = 0; u < RIX_WPI; u++) {
+            const int64_t i = g * (RIX_WPI * 64) + u * 64 + lane;
+            if (i < nvec) xv[i] = pat;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 64) {
+        if (lane < head) x[lane] = val;
+        if (tail0 + lane < n) x[tail0 + lane] = val;
+    }
+}
+
+// entry (i, j) -> X[i * ncols + j] (and 1 into its byte of Ab, when given); iso: vx holds one value
+template <class W>
+__global__ __launch_bounds__(RIX_BLOCK) void k_dense_scatter(int64_t nvals, int64_t nrows, int64_t ncols,
+                                                             const int64_t *__restrict__ rowptr,
+                                                             const int32_t *__restrict__ ci, const W *__restrict__ vx,
+                                                             bool iso, W *__restrict__ X, int8_t *__restrict__ Ab) {
+    const int lane = threadIdx.x & 63;
+    int64_t g0, g1;
+    rix_wave_chunks(nvals, g0, g1);
+    int64_t next = -1;
+    for (int64_t g = g0; g < g1; g++) {
+        const int64_t p0 = g * (RIX_WPI * 64);
+        int64_t row[RIX_WPI];
+        gb_chunk_rows<RIX_WPI>(rowptr, nrows, nvals, p0, lane, next, row);
+#pragma unroll
+        for (int u = 0; u < RIX_WPI; u++) {
+            const int64_t p = p0 + u * 64 + lane;
+            if (p >= nvals) continue;
+            const int64_t lin = row[u] * ncols + (int64_t)ci[p];
+            X[lin] = vx[iso ? 0 : p];
+            if (Ab) Ab[lin] = 1;
+        }
+    }
+}
+
+// a vector's bitmap to a dense array: X[p] = bit p ? dense[p] (dense[0] when iso) : fill, Ab[p] = bit p
+template <class W>
+__global__ __launch_bounds__(RIX_BLOCK) void k_bitmap_dense(int64_t n, const uint64_t *__restrict__ bits,
+                                                            const W *__restrict__ dense, bool iso, W fill,
+                                                            W *__restrict__ X, int8_t *__restrict__ Ab) {
+    const int lane = threadIdx.x & 63;
+    int64_t g0, g1;
+    rix_wave_chunks(n, g0, g1);
+    for (int64_t g = g0; g < g1; g++) {
+#pragma unroll
+        for (int u = 0; u < RIX_WPI; u++) {
+            const int64_t p = g * (RIX_WPI * 64) + u * 64 + lane;
+            if (p >= n) continue;
+            const bool bit = (bits[p >> 6] >> lane) & 1ULL;
+            X[p] = bit ? dense[iso ? 0 : p] : fill;
+            if (Ab) Ab[p] = bit;
         }
     }
 }
@@ -445,9 +563,257 @@ void vector_flatten(GB_Obj *w, GB_Obj *A, bool by_col) {
     gb_install_bitmap(w, n, T.bits, T.dense, iso, nullptr);
 }
 
+// ---- dense import / export.  Layout: A(i, j) sits at X[i * ncols + j]; by_col (X[i + j * nrows])
+// is the row-major array of the transpose, so the import ends in gb_transpose_csr and the export
+// reads gb_get_csc's view: no strided access.  A dense array is a full bitmap in position order
+// once k_dense_flags has decided which positions hold entries, and bitmap_csr does the rest.
+
+// a GrB_Scalar argument read on the host and cast to type `code`: present = it holds a value
+struct dense_scalar {
+    bool present = false;
+    alignas(8) unsigned char bytes[8] = {};
+    template <class W>
+    W as() const {
+        W w;
+        memcpy(&w, bytes, sizeof(W));
+        return w;
+    }
+};
+
+GrB_Info read_dense_scalar(dense_scalar &v, const GrB_Scalar s, int code) {
+    if (!s) return GrB_SUCCESS;
+    GB_Obj *S = OBJ(s);
+    if (S->magic != GB_MAGIC) return GrB_UNINITIALIZED_OBJECT;
+    alignas(8) unsigned char own[8] = {};
+    GrB_Info r = GrB_DOMAIN_MISMATCH;
+    switch (S->type->code) {
+#define GB_READ(T, ctype)                                                 \
+    case GBAMD_T_##T:                                                     \
+        r = GrB_Scalar_extractElement_##T((ctype *)own, s);               \
+        break;
+        GB_FOR_EACH_TYPE(GB_READ)
+#undef GB_READ
+    }
+    if (r == GrB_NO_VALUE) return GrB_SUCCESS;
+    if (r != GrB_SUCCESS) return r;
+    gb_cast_scalar(v.bytes, code, own, S->type->code);
+    v.present = true;
+    return GrB_SUCCESS;
+}
+
+// what GrB_Matrix_new checks of a shape (both dimensions as columns, when the transpose is
+// built); returns the number of positions
+int64_t dense_positions(GrB_Index nrows, GrB_Index ncols, bool both) {
+    GB_REQUIRE(nrows <= GrB_INDEX_MAX && ncols <= GrB_INDEX_MAX, GrB_INVALID_VALUE, "dimension too large");
+    GB_REQUIRE(ncols < (1ULL << 31) && (!both || nrows < (1ULL << 31)), GrB_OUT_OF_MEMORY,
+               "matrix with >= 2^31 columns exceeds the device index width");
+    const u128 total = (u128)nrows * ncols;
+    GB_REQUIRE(total < ((u128)1 << 63), GrB_OUT_OF_MEMORY, "dense array of 2^63 or more positions");
+    return (int64_t)total;
+}
+
+// a host array's device copy, or the device array itself
+const void *dense_stage_in(const void *p, size_t bytes, bool on_device, gb_scratch &s) {
+    if (on_device || !p) return p;
+    char *d = s.get<char>(bytes);
+    gb_copy_h2d(d, p, bytes);
+    return d;
+}
+
+// bits (nw words, nw >= 1) = which of the n positions of X / Ab (device) hold an entry
+void dense_flags(int64_t n, int code, const void *X, const int8_t *Ab, const dense_scalar &m, uint64_t *bits) {
+    auto go = [&](auto c) {
+        using C = decltype(c);
+        hipLaunchKernelGGL((k_dense_flags<C>), dim3(chunk_grid(n)), dim3(RIX_BLOCK), 0, gb_stream(), n, (const C *)X,
+                           Ab, m.present, m.as<C>(), bits);
+    };
+    if (!m.present) go(uint8_t());  // X is not read
+    else if (code == GBAMD_T_FP32) go(float());
+    else if (code == GBAMD_T_FP64) go(double());
+    else gb_with_size(gb_type_size(code), go);
+    GB_LAUNCH_CHECK();
+}
+
+// the CSR of nrows x ncols of the dense array X / Ab (device pointers), in X's type
+gb_mat_result dense_to_csr(int code, int64_t nrows, int64_t ncols, int64_t n, const void *X, const int8_t *Ab,
+                           const dense_scalar &m, bool by_col) {
+    gb_stat_set("reshape_div64", n > (int64_t)UINT32_MAX);
+    if (n == 0) return gb_empty_mat_result(nrows, ncols, code);
+    const int64_t tr = by_col ? ncols : nrows, tc = by_col ? nrows : ncols;
+    gb_scratch s;
+    uint64_t *bits = s.get<uint64_t>(gb_words(n));
+    dense_flags(n, code, X, Ab, m, bits);
+    gb_bitmap_view u;
+    u.n = n;
+    u.bits = bits;
+    u.vals = X;
+    u.tcode = code;
+    gb_mat_result T = bitmap_csr(u, false, tr, tc, 0, tc);
+    if (!by_col) return T;
+    auto release = [&] {
+        gb_free(T.rowptr);
+        gb_free(T.colidx);
+        gb_free(T.vals);
+    };
+    gb_mat_result R = T;
+    R.nrows = nrows;
+    R.ncols = ncols;
+    try {
+        if (T.nvals == 0) R = gb_empty_mat_result(nrows, ncols, code);
+        else
+            gb_transpose_csr(tr, tc, T.nvals, T.rowptr, T.colidx, T.vals, gb_type_size(code), false, &R.rowptr,
+                             &R.colidx, &R.vals);
+    } catch (...) {
+        release();
+        throw;
+    }
+    release();
+    return R;
+}
+
+void fill_array(int64_t n, size_t ts, void *X, const dense_scalar &fill) {
+    gb_with_size(ts, [&](auto w) {
+        using W = decltype(w);
+        hipLaunchKernelGGL((k_dense_fill<W>), dim3(chunk_grid(n * (int64_t)sizeof(W) / 16)), dim3(RIX_BLOCK), 0,
+                           gb_stream(), n, (W *)X, fill.as<W>());
+    });
+    GB_LAUNCH_CHECK();
+}
+
+// X / Ab (device, n positions) = the dense array of A, row-major, or of A' when by_col
+void csr_to_dense(GB_Obj *A, bool by_col, int64_t n, void *X, int8_t *Ab, const dense_scalar &fill) {
+    gb_csr_view v;
+    if (by_col) gb_get_csc(v, A);
+    else gb_get_csr(v, A);
+    const size_t ts = A->type->size;
+    if (v.nvals < n) {
+        fill_array(n, ts, X, fill);
+        if (Ab) fill_array(n, 1, Ab, dense_scalar());
+    }
+    if (v.nvals == 0) return;
+    gb_with_size(ts, [&](auto w) {
+        using W = decltype(w);
+        hipLaunchKernelGGL((k_dense_scatter<W>), dim3(chunk_grid(v.nvals)), dim3(RIX_BLOCK), 0, gb_stream(), v.nvals,
+                           v.nrows, v.ncols, v.rowptr, v.colidx, (const W *)v.vals, v.iso, (W *)X, Ab);
+    });
+    GB_LAUNCH_CHECK();
+}
+
+// the export of both kinds: A as nrows x ncols (a vector: size x 1, read off its bitmap)
+void export_dense(void *X, int8_t *Ab, GB_Obj *A, const dense_scalar &fill, bool by_col, bool on_device) {
+    const bool bitmap = A->kind != GB_KIND_MATRIX;
+    const u128 total = (u128)(uint64_t)A->nrows * (uint64_t)gb_ncols_of(A);
+    GB_REQUIRE(total < ((u128)1 << 63), GrB_OUT_OF_MEMORY, "dense array of 2^63 or more positions");
+    const int64_t n = (int64_t)total;
+    if (n == 0) return;
+    GB_REQUIRE(X, GrB_NULL_POINTER, "X is NULL");
+    GB_REQUIRE(fill.present || Ab || gb_nvals(A) == n, GrB_INVALID_VALUE,
+               "a fill value or a bitmap is needed when there are missing values");
+    const size_t ts = A->type->size;
+    gb_scratch s;
+    void *dX = on_device ? X : s.get<char>(n * ts);
+    int8_t *dAb = on_device || !Ab ? Ab : s.get<int8_t>(n);
+    if (bitmap) {
+        gb_bitmap_view u;
+        gb_get_bitmap(u, A);
+        gb_with_size(ts, [&](auto w) {
+            using W = decltype(w);
+            hipLaunchKernelGGL((k_bitmap_dense<W>), dim3(chunk_grid(n)), dim3(RIX_BLOCK), 0, gb_stream(), n, u.bits,
+                               (const W *)u.vals, u.iso, fill.as<W>(), (W *)dX, dAb);
+        });
+        GB_LAUNCH_CHECK();
+    } else {
+        csr_to_dense(A, by_col, n, dX, dAb, fill);
+    }
+    if (on_device) return;
+    gb_copy_d2h(X, dX, n * ts);
+    if (Ab) gb_copy_d2h(Ab, dAb, n);
+}
+
 }  // namespace
 
 extern "C" {
+
+GrB_Info GxB_Matrix_import_dense(GrB_Matrix *A, GrB_Type type, GrB_Index nrows, GrB_Index ncols, const void *X,
+                                 const int8_t *Ab, const GrB_Scalar missing, bool by_col, bool on_device) {
+    if (!A) return GrB_NULL_POINTER;
+    if (!type || type->magic != GB_MAGIC) return GrB_UNINITIALIZED_OBJECT;
+    dense_scalar m;
+    GrB_Info e = read_dense_scalar(m, missing, type->code);
+    if (e != GrB_SUCCESS) return e;
+    return gb_api(nullptr, [&] {
+        const int64_t n = dense_positions(nrows, ncols, by_col);
+        GB_REQUIRE(X || n == 0, GrB_NULL_POINTER, "X is NULL");
+        const int64_t nr = (int64_t)nrows, nc = (int64_t)ncols;
+        GB_Obj *Ao = gb_new_object_bare(GB_KIND_MATRIX, type, nr, nc);
+        try {
+            gb_scratch s;
+            const void *dX = dense_stage_in(X, n * type->size, on_device, s);
+            const int8_t *dAb = (const int8_t *)dense_stage_in(Ab, n, on_device, s);
+            gb_mat_result T = dense_to_csr(type->code, nr, nc, n, dX, dAb, m, by_col);
+            gb_install_csr(Ao, nr, nc, T.nvals, T.rowptr, T.colidx, T.vals, false);
+        } catch (...) {
+            free_bare(Ao);
+            throw;
+        }
+        *A = (GrB_Matrix)Ao;
+    });
+}
+
+GrB_Info GxB_Vector_import_dense(GrB_Vector *v, GrB_Type type, GrB_Index n, const void *X, const int8_t *Ab,
+                                 const GrB_Scalar missing, bool on_device) {
+    if (!v) return GrB_NULL_POINTER;
+    if (!type || type->magic != GB_MAGIC) return GrB_UNINITIALIZED_OBJECT;
+    dense_scalar m;
+    GrB_Info e = read_dense_scalar(m, missing, type->code);
+    if (e != GrB_SUCCESS) return e;
+    return gb_api(nullptr, [&] {
+        GB_REQUIRE(n <= GrB_INDEX_MAX, GrB_INVALID_VALUE, "dimension too large");
+        GB_REQUIRE(X || n == 0, GrB_NULL_POINTER, "X is NULL");
+        const int64_t size = (int64_t)n;
+        GB_Obj *vo = gb_new_object_bare(GB_KIND_VECTOR, type, size, 1);
+        try {
+            gb_vec_result T = gb_new_vec_result(size, type->code, false);
+            gb_free(T.d_nvals);  // recounted by the install
+            T.d_nvals = nullptr;
+            try {
+                if (size == 0) {
+                    gb_memset(T.bits, 0, sizeof(uint64_t));
+                } else {
+                    // the values are one copy; the words are the object's bitmap
+                    if (on_device) gb_copy_d2d(T.dense, X, size * type->size);
+                    else gb_copy_h2d(T.dense, X, size * type->size);
+                    gb_scratch s;
+                    const int8_t *dAb = (const int8_t *)dense_stage_in(Ab, size, on_device, s);
+                    dense_flags(size, type->code, T.dense, dAb, m, T.bits);
+                }
+            } catch (...) {
+                gb_free(T.bits);
+                gb_free(T.dense);
+                throw;
+            }
+            gb_install_bitmap(vo, size, T.bits, T.dense, false, nullptr);
+        } catch (...) {
+            free_bare(vo);
+            throw;
+        }
+        *v = (GrB_Vector)vo;
+    });
+}
+
+GrB_Info GxB_Matrix_export_dense(void *X, int8_t *Ab, const GrB_Matrix A, const GrB_Scalar fill, bool by_col,
+                                 bool on_device) {
+    if (!A) return GrB_NULL_POINTER;
+    if (OBJ(A)->magic != GB_MAGIC) return GrB_UNINITIALIZED_OBJECT;
+    dense_scalar f;
+    GrB_Info e = read_dense_scalar(f, fill, OBJ(A)->type->code);
+    if (e != GrB_SUCCESS) return e;
+    return gb_api(OBJ(A), [&] { export_dense(X, Ab, gb_obj_check(A), f, by_col, on_device); });
+}
+
+GrB_Info GxB_Vector_export_dense(void *X, int8_t *Ab, const GrB_Vector v, const GrB_Scalar fill, bool on_device) {
+    return GxB_Matrix_export_dense(X, Ab, (GrB_Matrix)v, fill, false, on_device);
+}
 
 GrB_Info GrB_Matrix_diag(GrB_Matrix *C, const GrB_Vector v, int64_t k) {
     if (!C) return GrB_NULL_POINTER;

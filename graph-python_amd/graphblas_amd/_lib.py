@@ -71,6 +71,10 @@ _SIGS = {
     "GrB_Matrix_diag": [P, P, L], "GxB_Matrix_diag": [P, P, L, P], "GxB_Vector_diag": [P, P, L, P],
     "GxB_Matrix_reshape": [P, ctypes.c_bool, I, I, P], "GxB_Matrix_reshapeDup": [P, P, ctypes.c_bool, I, I, P],
     "GxB_Vector_flatten": [P, P, ctypes.c_bool, P],
+    "GxB_Matrix_import_dense": [P, P, I, I, P, P, P, ctypes.c_bool, ctypes.c_bool],
+    "GxB_Vector_import_dense": [P, P, I, P, P, P, ctypes.c_bool],
+    "GxB_Matrix_export_dense": [P, P, P, P, ctypes.c_bool, ctypes.c_bool],
+    "GxB_Vector_export_dense": [P, P, P, P, ctypes.c_bool],
     "GrB_Vector_assign": [P, P, P, P, P, I, P], "GrB_Matrix_assign": [P, P, P, P, P, I, P, I, P],
     "GrB_Matrix_reduce_Monoid_Scalar": [P] * 5, "GrB_Vector_reduce_Monoid_Scalar": [P] * 5,
     "GrB_transpose": [P] * 5,

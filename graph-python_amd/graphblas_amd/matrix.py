@@ -182,6 +182,31 @@ class Matrix(BaseType):
               _CArray(vals, "values"), indptr.size, col_indices.size, vals.size, lib.GrB_CSR_FORMAT])
         return C
 
+    @classmethod
+    def from_dense(cls, values, missing_value=None, *, dtype=None, name=None, bitmap=None):
+        """The Matrix of a 2-d list, numpy array or device array (GxB_Matrix_import_dense; reference
+        core/matrix.py:1457-1518): every position holds an entry, but those equal to
+        ``missing_value`` and those whose byte of ``bitmap`` (same shape, order and residence) is 0."""
+        from .dense import from_dense
+
+        return from_dense(cls, values, missing_value, dtype, name, bitmap)
+
+    @classmethod
+    def from_scalar(cls, value, nrows, ncols, dtype=None, *, name=None):
+        """The full nrows x ncols Matrix of one value (reference core/matrix.py:1393-1455)."""
+        from .dense import from_scalar
+
+        return from_scalar(cls, value, (nrows, ncols), dtype, name)
+
+    def to_dense(self, fill_value=None, dtype=None, *, out=None, bitmap=None):
+        """The numpy array of this shape with ``fill_value`` where there is no entry
+        (GxB_Matrix_export_dense; reference core/matrix.py:1520-1574).  ``out``: a numpy or device
+        array in C or F order to fill in place (its dtype is the result's); ``bitmap``: an array of
+        the same shape, order and residence that receives 1 / 0 per position."""
+        from .dense import to_dense
+
+        return to_dense(self, fill_value, dtype, out, bitmap, upcast=True)
+
     def to_csr(self, dtype=None):
         dt = self.dtype if dtype is None else lookup_dtype(dtype)
         n = self.nvals
@@ -734,6 +759,12 @@ class TransposedMatrix:
         r, c, v = self._matrix.to_coo(*args, **kw)
         o = np.lexsort((r, c))
         return c[o], r[o], v[o]
+
+    def to_dense(self, fill_value=None, dtype=None, *, out=None, bitmap=None):
+        """As Matrix.to_dense: the column-major export of the matrix, nothing is transposed."""
+        from .dense import to_dense
+
+        return to_dense(self, fill_value, dtype, out, bitmap, upcast=True)
 
     def isequal(self, other, **kw):
         return self.new().isequal(other, **kw)

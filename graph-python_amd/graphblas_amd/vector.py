@@ -122,7 +122,33 @@ class Vector(BaseType):
         i, v = self.to_coo()
         return {int(a): x.item() for a, x in zip(i, v)}
 
-    def to_dense(self, fill_value=None, dtype=None):
+    @classmethod
+    def from_dense(cls, values, missing_value=None, *, dtype=None, name=None, bitmap=None):
+        """The Vector of a 1-d list, numpy array or device array (GxB_Vector_import_dense; reference
+        core/vector.py:894-946): every position holds an entry, but those equal to
+        ``missing_value`` and those whose byte of ``bitmap`` (same size and residence) is 0."""
+        from .dense import from_dense
+
+        return from_dense(cls, values, missing_value, dtype, name, bitmap)
+
+    @classmethod
+    def from_scalar(cls, value, size, dtype=None, *, name=None):
+        """The full Vector of one value (reference core/vector.py:835-892)."""
+        from .dense import from_scalar
+
+        return from_scalar(cls, value, (size,), dtype, name)
+
+    def to_dense(self, fill_value=None, dtype=None, *, out=None, bitmap=None):
+        """``out`` (a numpy or device array filled in place; its dtype is the result's) and ``bitmap``
+        (an array that receives 1 / 0 per position) go through GxB_Vector_export_dense."""
+        if out is not None or bitmap is not None:
+            from .dense import to_dense
+
+            return to_dense(self, fill_value, dtype, out, bitmap, upcast=False)
+        if fill_value is not None:
+            from .dense import _scalar_dtype
+
+            _scalar_dtype(fill_value, "fill_value", "to_dense")  # the reference's TypeError for a non-scalar
         i, v = self.to_coo(dtype)
         dt = v.dtype
         if fill_value is None:

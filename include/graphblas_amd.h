@@ -414,6 +414,32 @@ GrB_Info GxB_Matrix_reshape(GrB_Matrix C, bool by_col, GrB_Index nrows_new, GrB_
 GrB_Info GxB_Matrix_reshapeDup(GrB_Matrix *C, GrB_Matrix A, bool by_col, GrB_Index nrows_new,
                                GrB_Index ncols_new, const GrB_Descriptor desc);
 GrB_Info GxB_Vector_flatten(GrB_Vector w, const GrB_Matrix A, bool by_col, const GrB_Descriptor desc);
+/* dense import / export (reference core/matrix.py:1457-1574, core/vector.py:894-999; this library's
+ * own names: SuiteSparse's pack_FullR / pack_BitmapR hand over host malloc blocks, which device
+ * storage cannot take).  X holds nrows * ncols values -- of `type` on import, of the object's own
+ * type on export -- with A(i, j) at X[i * ncols + j], or at X[i + j * nrows] when by_col; Ab, when
+ * not NULL, is one byte per position in the same layout.  on_device false: host pointers, staged
+ * by one copy of X (and Ab) in each direction (the export synchronises); true: device pointers,
+ * read or written on the library stream.
+ * import: position p holds an entry iff (Ab == NULL or Ab[p] != 0) and (missing is NULL or empty,
+ * or X[p] != m), m = missing cast to `type`, != C's (a NaN m drops nothing, m = 0.0 drops both
+ * zeros).  Values are copied bit for bit; the result is never iso.  NULL A / v, or NULL X with at
+ * least one position: GrB_NULL_POINTER; a dimension GrB_Matrix_new refuses: its code (by_col builds
+ * the transpose, so both dimensions are columns once); nrows * ncols >= 2^63: GrB_OUT_OF_MEMORY.  A
+ * refused call leaves *A unset; zero positions touch no array.
+ * export: every position of X gets the entry's value or `fill` cast to the object's type; Ab, when
+ * given, gets 1 / 0 at every position.  fill NULL or empty: positions without an entry get zero
+ * bytes when Ab is given; without Ab an object that is not full is GrB_INVALID_VALUE and nothing
+ * is written. */
+GrB_Info GxB_Matrix_import_dense(GrB_Matrix *A, GrB_Type type, GrB_Index nrows, GrB_Index ncols,
+                                 const void *X, const int8_t *Ab, const GrB_Scalar missing,
+                                 bool by_col, bool on_device);
+GrB_Info GxB_Vector_import_dense(GrB_Vector *v, GrB_Type type, GrB_Index n,
+                                 const void *X, const int8_t *Ab, const GrB_Scalar missing, bool on_device);
+GrB_Info GxB_Matrix_export_dense(void *X, int8_t *Ab, const GrB_Matrix A, const GrB_Scalar fill,
+                                 bool by_col, bool on_device);
+GrB_Info GxB_Vector_export_dense(void *X, int8_t *Ab, const GrB_Vector v, const GrB_Scalar fill,
+                                 bool on_device);
 
 /* ---------------------------------------------------------------- the hot path */
 /* C<Mask> = C accum (A' (+).(x) B')      replaces SuiteSparse GrB_mxm */
