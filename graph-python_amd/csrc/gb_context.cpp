@@ -538,7 +538,7 @@ GrB_Info GxB_Global_get_int(const char *key, int64_t *value) {
     // defaults of its class bounds (gb_sort.hip)
     {
         bool mine = false;
-        const GrB_Info info = gb_api(nullptr, [&] { mine = gb_sort_stat(key, value); });
+        const GrB_Info info = gb_api(nullptr, [&] { mine = gb_sort_stat(key, value) || gb_selectk_stat(key, value); });
         if (mine || info != GrB_SUCCESS) return info;
     }
     // named kernel-class counters (gb_stat_add): "stat_" + name; 0 before the first count

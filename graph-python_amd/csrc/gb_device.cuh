@@ -557,6 +557,18 @@ GB_DEV T gb_shfl_down(T v, int delta, int width) {
 
 GB_DEV bool gb_bit(const uint64_t *bits, int64_t i) { return (bits[i >> 6] >> (i & 63)) & 1ULL; }
 
+// The random order of selectk / compactify: a stateless 64-bit hash of (seed, row, position),
+// two rounds of the splitmix64 finaliser over Weyl steps of the golden ratio.
+GB_DEV uint64_t gb_mix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+GB_DEV uint64_t gb_hash3(uint64_t seed, uint64_t row, uint64_t pos) {
+    const uint64_t g = 0x9E3779B97F4A7C15ull;
+    return gb_mix64(gb_mix64(seed + g * (row + 1)) + g * (pos + 1));
+}
+
 // ------------------------------------------------------------------ loops and searches
 // Shared by every operation file (the host-side counterparts are in gb_dispatch.cuh):
 // the grid-stride loop, the searches over a CSR's row pointers and column indices, and a

@@ -653,6 +653,45 @@ GB_Obj *gb_new_object_bare(int kind, GrB_Type type, int64_t nrows, int64_t ncols
 // asks here for "stat_sort_rows_{wave,block,long}" (rows each class took in the last matrix sort,
 // read from the device) and for the defaults of "sort_wave_max" / "sort_block_max"
 bool gb_sort_stat(const char *key, int64_t *value);
+// The sort's row classes at the service of selectk / compactify (gb_selectk.hip): the rows of a
+// CSR are ranked ascending by (key, position) and each entry is handed to a trimmed emit.  With
+// d the row's length, rank t is entry u = far ? d-1-t : t of the requested order; it is emitted
+// when u < m, at slot (reverse ? min(m, d)-1-u : u) of the output row that starts at orp[row].
+// keep != nullptr: nothing is moved, keep[input position] = 1 marks the emitted entries, and rows
+// of at most m entries are not ranked at all (the caller keeps them whole).
+struct gb_rank_job {
+    int64_t nrows = 0, nvals = 0;
+    const int64_t *rowptr = nullptr;
+    const int32_t *colidx = nullptr;
+    const void *xin = nullptr;  // the values as type xcode: the keys (not read when random)
+    int xcode = 0;
+    bool random = false;        // key = gb hash of (seed, row, position), 64 bits
+    uint64_t seed = 0;
+    const void *avals = nullptr;  // the values oC receives, vs bytes each
+    int vs = 0;
+    int64_t m = 0;
+    bool far = false, reverse = false;
+    const int64_t *orp = nullptr;
+    void *oC = nullptr;       // values (nullptr: not wanted)
+    int64_t *oP = nullptr;    // column indices (nullptr: not wanted)
+    int32_t *ocol = nullptr;  // the slots: the new column indices (nullptr with keep)
+    uint8_t *keep = nullptr;
+    int wave_max = 0, block_max = 0;     // 0: the sort's
+    unsigned long long *stats = nullptr;  // 4 zeroed device words: rows per class, as the sort's
+};
+void gb_rank_rows(const gb_rank_job &j);
+// The entries of a bitmap in the order of a mode: 0 by index, 1 ascending by (key of xin as
+// type xcode, index), 2 ascending by (hash of (seed, 0, position), index).  *idx: n slots, the
+// first nvals hold the entries' indices in that order; *off: words + 1 prefix counts, the last
+// one nvals.  Both live in s.
+void gb_bitmap_order(int64_t n, const uint64_t *bits, const void *xin, int xcode, bool iso, int mode, uint64_t seed,
+                     gb_scratch &s, int64_t **idx, int64_t **off);
+// the grid of a launch of these two files: gb_grid under the sort's cap, from one call site
+unsigned gb_sort_grid(int64_t items, int64_t per_block);
+
+// selectk / compactify (gb_selectk.hip): GxB_Global_get_int asks here for
+// "stat_selectk_rows_{all,wave,block,long}" and the defaults of "selectk_wave_max" / "selectk_block_max"
+bool gb_selectk_stat(const char *key, int64_t *value);
 
 // hash Gustavson C = A*B (gb_spgemm_hash.hip): flops = per-row product counts
 void gb_spgemm_hash(gb_mat_result &T, gb_csr_view &A, gb_csr_view &B, GrB_Semiring sr, bool iso,

@@ -114,11 +114,41 @@ struct sort_args {
     int64_t *blist, capB;       // rows of the block class up to SORT_SMALL_CAP entries
     int64_t *blist2, capB2;     // its longer rows
     int64_t *lbeg, *lend, capL;  // entry ranges of the long rows
+    int64_t *lrow;               // and the rows themselves
+    // the trimmed emit of gb_rank_rows (gb_internal.h, gb_rank_job); a sort emits every rank in place:
+    // orp = nullptr (the output rows are the input's), m = INT64_MAX, the rest unset
+    const int64_t *orp;
+    int64_t m;
+    bool far, reverse;
+    uint8_t *keep;
+    uint64_t seed;  // of the random order (X = sort_rnd)
 };
 
-// output entry q = input entry p of the same row, rank t
-GB_DEV void sort_emit(const sort_args &a, int64_t q, int64_t p, int32_t t) {
-    a.ocol[q] = t;
+// the key type of the random order: nothing is read, the key is a hash of (seed, row, position)
+struct sort_rnd {
+    uint64_t x;
+};
+
+// the key of entry t of the row `row` that starts at s
+template <class X>
+GB_DEV uint64_t sort_key_at(const sort_args &a, const X *__restrict__ xin, int64_t row, int64_t s, int64_t t) {
+    if constexpr (std::is_same<X, sort_rnd>::value) return gb_hash3(a.seed, (uint64_t)row, (uint64_t)t);
+    else return sort_key<X>(xin[s + t]) ^ a.flip;
+}
+
+// rank t of a row of len entries (its output row starts at os) is input entry p: entry
+// u = far ? len-1-t : t of the requested order, emitted when u < m at slot u, or
+// min(m, len)-1-u under reverse; with keep it is only marked
+GB_DEV void sort_emit(const sort_args &a, int64_t os, int64_t len, int64_t p, int32_t t) {
+    const int64_t u = a.far ? len - 1 - t : t;
+    if (u >= a.m) return;
+    if (a.keep) {
+        a.keep[p] = 1;
+        return;
+    }
+    const int64_t slot = a.reverse ? min(a.m, len) - 1 - u : u;
+    const int64_t q = os + slot;
+    a.ocol[q] = (int32_t)slot;
     if (a.oP) a.oP[q] = a.colidx[p];
     if (a.oC) {
         switch (a.vs) {
@@ -155,12 +185,14 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_sort_wave(sort_args a) {
     for (int64_t base = ((blockIdx.x * (int64_t)SORT_BLOCK + threadIdx.x) >> 6) << 6; base < a.nrows;
          base += nwaves << 6) {
         const int64_t i = base + lane;
-        int64_t s = 0, len = 0;
+        int64_t s = 0, len = 0, os = 0;
         if (i < a.nrows) {
             s = a.rowptr[i];
             len = a.rowptr[i + 1] - s;
+            os = a.orp ? a.orp[i] : s;
+            if (a.keep && len <= a.m) len = 0;  // kept whole by the caller
         }
-        if (len == 1 && !a.all_long) sort_emit(a, s, s, 0);
+        if (len == 1 && !a.all_long) sort_emit(a, os, 1, s, 0);
         const bool isl = len >= 2 && (a.all_long || len > a.block_max);
         const bool isw = len >= 2 && !isl && len <= a.wave_max;
         const bool isb = len >= 2 && !isl && !isw && len <= SORT_SMALL_CAP;
@@ -189,6 +221,7 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_sort_wave(sort_args a) {
             if (isl && !a.all_long && slot < a.capL) {
                 a.lbeg[slot] = s;
                 a.lend[slot] = s + len;
+                a.lrow[slot] = i;
             }
         }
         if (!mw) continue;
@@ -202,10 +235,11 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_sort_wave(sort_args a) {
                 const int n = done + g;
                 const int src = n < total ? sort_nth_set(m, n) : 0;
                 const int64_t rs = (int64_t)__shfl((unsigned long long)s, src);
+                const int64_t ros = (int64_t)__shfl((unsigned long long)os, src);
                 int rl = __shfl(ilen, src);
                 if (n >= total) rl = 0;
                 E e = E::pad((uint32_t)t);
-                if (t < rl) e = E::make(sort_key<X>(xin[rs + t]) ^ a.flip, (uint32_t)t);
+                if (t < rl) e = E::make(sort_key_at<X>(a, xin, base + src, rs, t), (uint32_t)t);
                 for (int k = 2; k <= G; k <<= 1) {
                     for (int j = k >> 1; j > 0; j >>= 1) {
                         const E o = e.xchg(j);
@@ -213,7 +247,7 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_sort_wave(sort_args a) {
                         if (take_min ? o.less(e) : e.less(o)) e = o;
                     }
                 }
-                if (t < rl) sort_emit(a, rs + t, rs + e.pos(), t);
+                if (t < rl) sort_emit(a, ros, rl, rs + e.pos(), t);
             }
         }
     }
@@ -245,10 +279,11 @@ __global__ __launch_bounds__(THREADS) void k_sort_block(sort_args a) {
         const int64_t i = list[b];
         const int64_t s = a.rowptr[i];
         const int len = (int)min(a.rowptr[i + 1] - s, (int64_t)CAP);
+        const int64_t os = a.orp ? a.orp[i] : s;
         int N = 2;
         while (N < len) N <<= 1;
         for (int t = tid; t < N; t += THREADS)
-            store(t, t < len ? E::make(sort_key<X>(xin[s + t]) ^ a.flip, (uint32_t)t) : E::pad((uint32_t)t));
+            store(t, t < len ? E::make(sort_key_at<X>(a, xin, i, s, t), (uint32_t)t) : E::pad((uint32_t)t));
         __syncthreads();
         for (int k = 2; k <= N; k <<= 1) {
             for (int j = k >> 1; j > 0; j >>= 1) {
@@ -264,7 +299,7 @@ __global__ __launch_bounds__(THREADS) void k_sort_block(sort_args a) {
                 __syncthreads();
             }
         }
-        for (int t = tid; t < len; t += THREADS) sort_emit(a, s + t, s + load(t).pos(), t);
+        for (int t = tid; t < len; t += THREADS) sort_emit(a, os, len, s + load(t).pos(), t);
         __syncthreads();
     }
 }
@@ -276,9 +311,9 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_sort_long_keys(sort_args a, K *_
     const X *__restrict__ xin = (const X *)a.xin;
     const int64_t cnt = min((int64_t)a.stats[2], a.capL);
     for (int64_t b = blockIdx.x; b < cnt; b += gridDim.x) {
-        const int64_t e = min(a.lend[b], a.nvals);
-        for (int64_t p = a.lbeg[b] + threadIdx.x; p < e; p += SORT_BLOCK) {
-            keys[p] = (K)(sort_key<X>(xin[p]) ^ a.flip);
+        const int64_t s = a.lbeg[b], e = min(a.lend[b], a.nvals), row = a.lrow[b];
+        for (int64_t p = s + threadIdx.x; p < e; p += SORT_BLOCK) {
+            keys[p] = (K)sort_key_at<X>(a, xin, row, s, p - s);
             pay[p] = (uint32_t)p;
         }
     }
@@ -288,7 +323,8 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_sort_long_emit(sort_args a, cons
     const int64_t cnt = min((int64_t)a.stats[2], a.capL);
     for (int64_t b = blockIdx.x; b < cnt; b += gridDim.x) {
         const int64_t s = a.lbeg[b], e = min(a.lend[b], a.nvals);
-        for (int64_t q = s + threadIdx.x; q < e; q += SORT_BLOCK) sort_emit(a, q, pay[q], (int32_t)(q - s));
+        const int64_t os = a.orp ? a.orp[a.lrow[b]] : s;
+        for (int64_t q = s + threadIdx.x; q < e; q += SORT_BLOCK) sort_emit(a, os, e - s, pay[q], (int32_t)(q - s));
     }
 }
 
@@ -298,7 +334,7 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_sort_all_keys(sort_args a, K *__
                                                               uint32_t *__restrict__ pay) {
     const X *__restrict__ xin = (const X *)a.xin;
     for (int64_t p = blockIdx.x * (int64_t)SORT_BLOCK + threadIdx.x; p < a.nvals; p += (int64_t)gridDim.x * SORT_BLOCK) {
-        keys[p] = (K)(sort_key<X>(xin[p]) ^ a.flip);
+        keys[p] = (K)sort_key_at<X>(a, xin, 0, p, 0);
         pay[p] = (uint32_t)p;
     }
 }
@@ -313,7 +349,8 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_sort_all_emit(sort_args a, const
             if (a.rowptr[mid] > q) hi = mid;
             else lo = mid + 1;
         }
-        sort_emit(a, q, pay ? (int64_t)pay[q] : q, (int32_t)(q - a.rowptr[lo - 1]));
+        const int64_t s = a.rowptr[lo - 1];
+        sort_emit(a, s, a.rowptr[lo] - s, pay ? (int64_t)pay[q] : q, (int32_t)(q - s));
     }
 }
 
@@ -348,12 +385,19 @@ void sort_check_perm_type(GB_Obj *P) {
                    "the permutation must be GrB_INT64 or GrB_UINT64");
 }
 
+// f(X()) with X the key type: sort_rnd for the random order (xcode < 0), else the type of xcode
+template <class F>
+void sort_with_key(int xcode, F &&f) {
+    if (xcode < 0) f(sort_rnd());
+    else gb_with_type(xcode, f);
+}
+
 template <class K>
 void sort_segments(sort_args &a, int xcode, int key_bits, int64_t nseg, const int64_t *beg, const int64_t *end,
                    gb_scratch &s) {
     K *kin = s.get<K>(a.nvals), *kout = s.get<K>(a.nvals);
     uint32_t *pin = s.get<uint32_t>(a.nvals), *pout = s.get<uint32_t>(a.nvals);
-    gb_with_type(xcode, [&](auto xv) {
+    sort_with_key(xcode, [&](auto xv) {
         using X = decltype(xv);
         if (a.all_long)
             hipLaunchKernelGGL((k_sort_all_keys<X, K>), dim3(gb_grid(a.nvals, SORT_BLOCK, sort_cap())),
@@ -376,6 +420,39 @@ void sort_segments(sort_args &a, int xcode, int key_bits, int64_t nseg, const in
         hipLaunchKernelGGL(k_sort_long_emit, dim3(gb_grid(nseg, 1, sort_cap())), dim3(SORT_BLOCK), 0, gb_stream(), a,
                            (const uint32_t *)pout);
     GB_LAUNCH_CHECK();
+}
+
+// the three row classes over the rows of a (bounds, key type and outputs set by the caller; xcode < 0:
+// the random order): the lists, the kernels, and the segmented radix sort of the long rows
+void sort_classes(sort_args &a, int xcode, int key_bits, gb_scratch &s) {
+    // a row of a class is longer than the class below allows: that bounds the lists
+    a.capB = a.all_long ? 0 : std::min(a.nrows, a.nvals / (a.wave_max + 1));
+    a.capB2 = a.all_long || a.block_max <= SORT_SMALL_CAP ? 0 : std::min(a.nrows, a.nvals / (SORT_SMALL_CAP + 1));
+    a.capL = a.all_long ? 0 : std::min(a.nrows, a.nvals / (a.block_max + 1));
+    a.blist = s.get<int64_t>(a.capB);
+    a.blist2 = s.get<int64_t>(a.capB2);
+    a.lbeg = s.get<int64_t>(3 * a.capL);
+    a.lend = a.lbeg + a.capL;
+    a.lrow = a.lend + a.capL;
+    if (a.capL) gb_memset(a.lbeg, 0, 3 * a.capL * sizeof(int64_t));
+    sort_with_key(xcode, [&](auto xv) {
+        using X = decltype(xv);
+        hipLaunchKernelGGL(k_sort_wave<X>, dim3(gb_sort_grid(a.nrows, 256)), dim3(SORT_BLOCK), 0,
+                           gb_stream(), a);
+        if (a.capB)
+            hipLaunchKernelGGL((k_sort_block<X, SORT_SMALL_CAP, 64>), dim3(gb_grid(a.capB, 1, sort_cap())),
+                               dim3(64), 0, gb_stream(), a);
+        if (a.capB2)
+            hipLaunchKernelGGL((k_sort_block<X, SORT_BLOCK_CAP, SORT_BLOCK>),
+                               dim3(gb_grid(a.capB2, 1, sort_cap(4096))), dim3(SORT_BLOCK), 0, gb_stream(), a);
+    });
+    GB_LAUNCH_CHECK();
+    if (a.all_long || a.capL) {
+        const int64_t nseg = a.all_long ? a.nrows : a.capL;
+        const int64_t *beg = a.all_long ? a.rowptr : a.lbeg, *end = a.all_long ? a.rowptr + 1 : a.lend;
+        if (key_bits == 64) sort_segments<uint64_t>(a, xcode, key_bits, nseg, beg, end, s);
+        else sort_segments<uint32_t>(a, xcode, key_bits, nseg, beg, end, s);
+    }
 }
 
 void matrix_sort(GB_Obj *C, GB_Obj *P, GrB_BinaryOp op, GB_Obj *A, const gb_desc &d) {
@@ -423,6 +500,7 @@ void matrix_sort(GB_Obj *C, GB_Obj *P, GrB_BinaryOp op, GB_Obj *A, const gb_desc
         a.oP = pvals;
         a.ocol = ocol;
         a.stats = g_sort_stats;
+        a.m = INT64_MAX;
         if (v.iso) {
             if (C) gb_copy_d2d(cvals, v.vals, vs);
             hipLaunchKernelGGL(k_sort_all_emit, dim3(gb_grid(nv, SORT_BLOCK, sort_cap())), dim3(SORT_BLOCK), 0,
@@ -435,33 +513,7 @@ void matrix_sort(GB_Obj *C, GB_Obj *P, GrB_BinaryOp op, GB_Obj *A, const gb_desc
             a.wave_max = sort_knob("sort_wave_max", SORT_WAVE_CAP);
             a.block_max = std::max(a.wave_max, sort_knob("sort_block_max", SORT_BLOCK_CAP));
             a.all_long = gb_knob("sort_method") == 1;
-            // a row of a class is longer than the class below allows: that bounds the lists
-            a.capB = a.all_long ? 0 : std::min(v.nrows, nv / (a.wave_max + 1));
-            a.capB2 = a.all_long || a.block_max <= SORT_SMALL_CAP ? 0 : std::min(v.nrows, nv / (SORT_SMALL_CAP + 1));
-            a.capL = a.all_long ? 0 : std::min(v.nrows, nv / (a.block_max + 1));
-            a.blist = s.get<int64_t>(a.capB);
-            a.blist2 = s.get<int64_t>(a.capB2);
-            a.lbeg = s.get<int64_t>(2 * a.capL);
-            a.lend = a.lbeg + a.capL;
-            if (a.capL) gb_memset(a.lbeg, 0, 2 * a.capL * sizeof(int64_t));
-            gb_with_type(xcode, [&](auto xv) {
-                using X = decltype(xv);
-                hipLaunchKernelGGL(k_sort_wave<X>, dim3(gb_grid(v.nrows, 256, sort_cap())), dim3(SORT_BLOCK), 0,
-                                   gb_stream(), a);
-                if (a.capB)
-                    hipLaunchKernelGGL((k_sort_block<X, SORT_SMALL_CAP, 64>), dim3(gb_grid(a.capB, 1, sort_cap())),
-                                       dim3(64), 0, gb_stream(), a);
-                if (a.capB2)
-                    hipLaunchKernelGGL((k_sort_block<X, SORT_BLOCK_CAP, SORT_BLOCK>),
-                                       dim3(gb_grid(a.capB2, 1, sort_cap(4096))), dim3(SORT_BLOCK), 0, gb_stream(), a);
-            });
-            GB_LAUNCH_CHECK();
-            if (a.all_long || a.capL) {
-                const int64_t nseg = a.all_long ? v.nrows : a.capL;
-                const int64_t *beg = a.all_long ? v.rowptr : a.lbeg, *end = a.all_long ? v.rowptr + 1 : a.lend;
-                if (key_bits == 64) sort_segments<uint64_t>(a, xcode, key_bits, nseg, beg, end, s);
-                else sort_segments<uint32_t>(a, xcode, key_bits, nseg, beg, end, s);
-            }
+            sort_classes(a, xcode, key_bits, s);
         }
     }
     // one result per requested output; under T0 back to CSR through the transpose
@@ -512,12 +564,14 @@ __global__ void k_sort_vec_pop(const uint64_t *__restrict__ bits, int64_t n, int
     }
 }
 
-// slot k < nvals: the k-th entry's index and key; slots from nvals on: the pad
+// slot k < nvals: the k-th entry's index and key (X = sort_rnd: the hash of (seed, 0, k); keys =
+// nullptr: none); slots from nvals on: the pad
 template <class X>
 __global__ __launch_bounds__(SORT_BLOCK) void k_sort_vec_compact(int64_t n, const uint64_t *__restrict__ bits,
                                                                  const int64_t *__restrict__ off,
                                                                  const X *__restrict__ xin, bool iso, uint64_t flip,
-                                                                 uint64_t padkey, uint64_t *__restrict__ keys,
+                                                                 uint64_t padkey, uint64_t seed,
+                                                                 uint64_t *__restrict__ keys,
                                                                  int64_t *__restrict__ idx) {
     const int64_t nvals = off[(n + 63) >> 6];
     for (int64_t i = blockIdx.x * (int64_t)SORT_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * SORT_BLOCK) {
@@ -525,11 +579,15 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_sort_vec_compact(int64_t n, cons
         if ((b >> (i & 63)) & 1) {
             const int64_t slot = off[i >> 6] + __popcll(b & ((1ull << (i & 63)) - 1));
             idx[slot] = i;
-            keys[slot] = sort_key<X>(xin[iso ? 0 : i]) ^ flip;
+            if constexpr (std::is_same<X, sort_rnd>::value) {
+                if (keys) keys[slot] = gb_hash3(seed, 0, (uint64_t)slot);
+            } else {
+                keys[slot] = sort_key<X>(xin[iso ? 0 : i]) ^ flip;
+            }
         }
         if (i >= nvals) {
             idx[i] = 0;
-            keys[i] = padkey;
+            if (keys) keys[i] = padkey;
         }
     }
 }
@@ -566,6 +624,30 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_sort_vec_emit(int64_t n, const i
     }
 }
 
+// gb_bitmap_order (gb_internal.h); desc: the descending value order
+void bitmap_order(int64_t n, const uint64_t *bits, const void *xin, int xcode, bool iso, bool desc, int mode,
+                  uint64_t seed, gb_scratch &s, int64_t **pidx, int64_t **poff) {
+    const int64_t nw = gb_words(n);
+    int64_t *pop = s.get<int64_t>(nw), *off = s.get<int64_t>(nw + 1);
+    const bool sorts = mode == 2 || (mode == 1 && !iso);  // equal keys keep their index order
+    uint64_t *keys = sorts || mode == 1 ? s.get<uint64_t>(n) : nullptr;
+    int64_t *idx = s.get<int64_t>(n);
+    hipLaunchKernelGGL(k_sort_vec_pop, dim3(gb_grid(nw, 256, sort_cap())), dim3(256), 0, gb_stream(), bits, n, nw, pop);
+    GB_LAUNCH_CHECK();
+    gb_exclusive_scan_i64(pop, off, nw);
+    const int key_bits = mode == 1 ? 8 * (int)gb_type_size(xcode) : 64;
+    const uint64_t ones = key_bits == 64 ? ~0ull : (1ull << key_bits) - 1;
+    sort_with_key(mode == 1 ? xcode : -1, [&](auto xv) {
+        using X = decltype(xv);
+        hipLaunchKernelGGL(k_sort_vec_compact<X>, dim3(gb_sort_grid(n, SORT_BLOCK)), dim3(SORT_BLOCK), 0, gb_stream(),
+                           n, bits, off, (const X *)xin, iso, desc ? ones : 0, ones, seed, keys, idx);
+    });
+    GB_LAUNCH_CHECK();
+    if (sorts) gb_sort_pairs_u64(keys, idx, n, key_bits);
+    *pidx = idx;
+    *poff = off;
+}
+
 void vector_sort(GB_Obj *W, GB_Obj *P, GrB_BinaryOp op, GB_Obj *U) {
     GB_REQUIRE(W || P, GrB_NULL_POINTER, "both outputs are NULL");
     bool desc = false;
@@ -589,24 +671,9 @@ void vector_sort(GB_Obj *W, GB_Obj *P, GrB_BinaryOp op, GB_Obj *U) {
         if (P) gb_memset(TP.d_nvals, 0, sizeof(int64_t));
     } else {
         gb_scratch s;
-        int64_t *pop = s.get<int64_t>(nw), *off = s.get<int64_t>(nw + 1);
-        uint64_t *keys = s.get<uint64_t>(n);
-        int64_t *idx = s.get<int64_t>(n);
+        int64_t *idx, *off;
         const unsigned grid = gb_grid(n, SORT_BLOCK, sort_cap());
-        hipLaunchKernelGGL(k_sort_vec_pop, dim3(gb_grid(nw, 256, sort_cap())), dim3(256), 0, gb_stream(), uv.bits, n,
-                           nw, pop);
-        GB_LAUNCH_CHECK();
-        gb_exclusive_scan_i64(pop, off, nw);
-        const int key_bits = 8 * (int)gb_type_size(xcode);
-        const uint64_t ones = key_bits == 64 ? ~0ull : (1ull << key_bits) - 1;
-        const void *xin = gb_bitmap_vals_as(uv, xcode, s);
-        gb_with_type(xcode, [&](auto xv) {
-            using X = decltype(xv);
-            hipLaunchKernelGGL(k_sort_vec_compact<X>, dim3(grid), dim3(SORT_BLOCK), 0, gb_stream(), n, uv.bits, off,
-                               (const X *)xin, uv.iso, desc ? ones : 0, ones, keys, idx);
-        });
-        GB_LAUNCH_CHECK();
-        if (!uv.iso) gb_sort_pairs_u64(keys, idx, n, key_bits);  // equal keys keep their index order
+        bitmap_order(n, uv.bits, gb_bitmap_vals_as(uv, xcode, s), xcode, uv.iso, desc, 1, 0, s, &idx, &off);
         if (W && uv.iso) gb_copy_d2d(TW.dense, uv.vals, vs);
         hipLaunchKernelGGL(k_sort_vec_emit, dim3(grid), dim3(SORT_BLOCK), 0, gb_stream(), n, off, idx, uv.vals, (int)vs,
                            W && !uv.iso ? TW.dense : nullptr, P ? (int64_t *)TP.dense : nullptr, W ? TW.bits : nullptr,
@@ -619,6 +686,41 @@ void vector_sort(GB_Obj *W, GB_Obj *P, GrB_BinaryOp op, GB_Obj *U) {
 }
 
 }  // namespace
+
+unsigned gb_sort_grid(int64_t items, int64_t per_block) { return gb_grid(items, per_block, sort_cap()); }
+
+void gb_bitmap_order(int64_t n, const uint64_t *bits, const void *xin, int xcode, bool iso, int mode, uint64_t seed,
+                     gb_scratch &s, int64_t **idx, int64_t **off) {
+    bitmap_order(n, bits, xin, xcode, iso, false, mode, seed, s, idx, off);
+}
+
+void gb_rank_rows(const gb_rank_job &j) {
+    GB_REQUIRE(j.nvals < (1LL << 31) && j.nrows < (1LL << 31), GrB_NOT_IMPLEMENTED,
+               "selection by value or at random among 2^31 or more entries or rows");
+    gb_scratch s;
+    sort_args a{};
+    a.nrows = j.nrows;
+    a.nvals = j.nvals;
+    a.rowptr = j.rowptr;
+    a.colidx = j.colidx;
+    a.xin = j.xin;
+    a.avals = j.avals;
+    a.vs = j.vs;
+    a.oC = j.oC;
+    a.oP = j.oP;
+    a.ocol = j.ocol;
+    a.stats = j.stats;
+    a.orp = j.orp;
+    a.m = j.m;
+    a.far = j.far;
+    a.reverse = j.reverse;
+    a.keep = j.keep;
+    a.seed = j.seed;
+    a.wave_max = j.wave_max > 0 ? std::min(j.wave_max, SORT_WAVE_CAP) : sort_knob("sort_wave_max", SORT_WAVE_CAP);
+    a.block_max = j.block_max > 0 ? std::min(j.block_max, SORT_BLOCK_CAP) : sort_knob("sort_block_max", SORT_BLOCK_CAP);
+    a.block_max = std::max(a.wave_max, a.block_max);
+    sort_classes(a, j.random ? -1 : j.xcode, j.random ? 64 : 8 * (int)gb_type_size(j.xcode), s);
+}
 
 bool gb_sort_stat(const char *key, int64_t *value) {
     static const char *names[3] = {"stat_sort_rows_wave", "stat_sort_rows_block", "stat_sort_rows_long"};

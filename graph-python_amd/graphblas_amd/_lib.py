@@ -66,6 +66,10 @@ _SIGS = {
     "GrB_Matrix_kronecker_BinaryOp": [P] * 7, "GrB_Matrix_kronecker_Monoid": [P] * 7,
     "GrB_Matrix_kronecker_Semiring": [P] * 7,
     "GxB_Matrix_sort": [P] * 5, "GxB_Vector_sort": [P] * 5,
+    "GxB_Matrix_selectk": [P, P, E, I, U, P], "GxB_Vector_selectk": [P, P, E, I, U, P],
+    "GxB_Matrix_compactify": [P, P, E, I, ctypes.c_bool, ctypes.c_bool, U, P],
+    "GxB_Vector_compactify": [P, P, E, I, ctypes.c_bool, ctypes.c_bool, U, P],
+    "GxB_Matrix_compactify_width": [P, P, P],
     "GxB_Matrix_eWiseUnion": [P] * 9, "GxB_Vector_eWiseUnion": [P] * 9,
     "GxB_Matrix_concat": [P, P, I, I, P], "GxB_Matrix_split": [P, I, I, P, P, P, P],
     "GrB_Matrix_diag": [P, P, L], "GxB_Matrix_diag": [P, P, L, P], "GxB_Vector_diag": [P, P, L, P],
@@ -152,6 +156,8 @@ ENUMS = {
     "GrB_OUTP": 0, "GrB_MASK": 1, "GrB_INP0": 2, "GrB_INP1": 3, "GxB_DEFAULT": 0,
     "GrB_REPLACE": 1, "GrB_COMP": 2, "GrB_STRUCTURE": 4, "GrB_COMP_STRUCTURE": 6, "GrB_TRAN": 3,
     "GrB_CSR_FORMAT": 0, "GrB_CSC_FORMAT": 1, "GrB_COO_FORMAT": 2,
+    "GxB_SELECTK_FIRST": 0, "GxB_SELECTK_LAST": 1, "GxB_SELECTK_SMALLEST": 2, "GxB_SELECTK_LARGEST": 3,
+    "GxB_SELECTK_RANDOM": 4,
 }
 
 

@@ -15,6 +15,11 @@ segmented sort on the device, nothing goes through the host.  The k largest
 entries of every row are ``C, P = A.ss.sort(">")`` followed by
 ``C.select("col<=", k - 1)`` (and the same select of ``P`` for where they came from).
 
+``selectk`` / ``compactify`` are one call of GxB_*_selectk / GxB_*_compactify (csrc/gb_selectk.hip):
+up to k entries of every row, chosen by position, by value or at random, kept in place or moved to
+the left; the k largest of every row with their columns are ``A.ss.compactify("largest", k)`` and
+``A.ss.compactify("largest", k, asindex=True)``, without sorting or writing the rest of the row.
+
 ``split`` / ``concat`` are one call of GxB_Matrix_split / GxB_Matrix_concat (csrc/gb_tile.hip)
 whatever the number of tiles; vectors go through the same two entry points as N x 1 objects, as
 in the reference (core/ss/matrix.py:281-381, core/ss/vector.py:185-265, ss/_core.py:73-107).
@@ -448,6 +453,44 @@ def _sort_opts(opts):
     return opts
 
 
+_HOWS = {"first": 0, "last": 1, "smallest": 2, "largest": 3, "random": 4}  # GxB_SelectK_How
+_SELECTK_HOWS = '`how` argument must be one of: "random", "first", "last", "largest", "smallest"'
+_COMPACTIFY_HOWS = '`how` argument must be one of: "first", "last", "smallest", "largest", "random"'
+
+
+def _how(how, message):
+    key = how.lower() if isinstance(how, str) else how
+    if key not in _HOWS:
+        raise ValueError(message)
+    return _HOWS[key]
+
+
+def _count(k):
+    if k < 0:
+        raise ValueError("negative k is not allowed")
+    return int(k)
+
+
+def _seed(seed):
+    """The 64 bits of the random order: ``seed``, or a draw from ``numpy.random``'s global state
+    (so that ``np.random.seed`` governs a run, as it does for the reference)."""
+    if seed is None:
+        return int(np.random.randint(0, 1 << 64, dtype=np.uint64))
+    return int(seed) & ((1 << 64) - 1)
+
+
+class _IndexOut:
+    """A ``GrB_Index *`` result."""
+
+    def __init__(self, name):
+        self.value = ctypes.c_uint64()
+        self.name = name
+
+    @property
+    def _carg(self):
+        return ctypes.byref(self.value)
+
+
 class VectorSS:
     def __init__(self, parent):
         self._parent = parent
@@ -471,6 +514,37 @@ class VectorSS:
         p = Vector(UINT64, parent.size, name="Permutation") if permutation else None
         call("GxB_Vector_sort", [w, p, op, parent, desc])
         return w, p
+
+    def selectk(self, how, k, *, seed=None, name=None):
+        """GxB_Vector_selectk (reference core/ss/vector.py:1407-1454): up to ``k`` entries, each at
+        its own index.  ``how``: "first", "last", "smallest", "largest" (ties by position, see
+        include/graphblas_amd.h) or "random" (a uniform k-subset; ``seed`` reproduces it)."""
+        from .vector import Vector
+
+        parent = self._parent
+        how = _how(how, _SELECTK_HOWS)
+        k = _count(k)
+        w = Vector(parent.dtype, parent._size, name=name)
+        call("GxB_Vector_selectk", [w, parent, how, k, _seed(seed), None])
+        return w
+
+    def compactify(self, how="first", size=None, *, reverse=False, asindex=False, seed=None, name=None):
+        """GxB_Vector_compactify (reference core/ss/vector.py:1456-1560): the entries moved to
+        positions 0 .. in the order of ``how`` (reversed if ``reverse``), as values or, with
+        ``asindex``, as the indices they came from (UINT64), in a new Vector of ``size`` positions
+        (default: nvals).  "random" emits its choice in ascending index and ignores ``reverse``."""
+        from .vector import Vector
+
+        parent = self._parent
+        how = _how(how, _COMPACTIFY_HOWS)
+        dtype = UINT64 if asindex else parent.dtype
+        if size is None:
+            size = parent.nvals
+        size = _count(size)
+        w = Vector(dtype, size, name=name)
+        if size:
+            call("GxB_Vector_compactify", [w, parent, how, size, bool(reverse), bool(asindex), _seed(seed), None])
+        return w
 
     def split(self, chunks, *, name=None):
         """GxB_Matrix_split of the vector as N x 1 (reference core/ss/vector.py:185-234): a list
@@ -548,6 +622,43 @@ class MatrixSS:
         P = Matrix(UINT64, parent.nrows, parent.ncols, name="Permutation") if permutation else None
         call("GxB_Matrix_sort", [C, P, op, parent, desc])
         return C, P
+
+    def selectk(self, how, k, order="rowwise", *, seed=None, name=None):
+        """GxB_Matrix_selectk (reference core/ss/matrix.py:3815-3875): up to ``k`` entries of every
+        row (column, if columnwise), each where it was.  ``how``: "first", "last", "smallest",
+        "largest" (ties by position, see include/graphblas_amd.h) or "random" (a uniform k-subset of
+        every row; ``seed`` reproduces it)."""
+        from .matrix import Matrix
+
+        parent = self._parent
+        columnwise = _order(order) == "columnwise"
+        how = _how(how, _SELECTK_HOWS)
+        k = _count(k)
+        C = Matrix(parent.dtype, parent._nrows, parent._ncols, name=name)
+        call("GxB_Matrix_selectk", [C, parent, how, k, _seed(seed), descriptor_lookup(transpose_first=columnwise)])
+        return C
+
+    def compactify(self, how="first", k=None, order="rowwise", *, reverse=False, asindex=False, seed=None, name=None):
+        """GxB_Matrix_compactify (reference core/ss/matrix.py:3877-3989): every row's entries moved
+        to columns 0 .. (every column's to rows 0 .., if columnwise) in the order of ``how``
+        (reversed if ``reverse``), as values or, with ``asindex``, as the column (row) indices they
+        came from (UINT64).  The new Matrix is nrows x k (k x ncols); ``k`` defaults to the longest
+        row (column).  "random" emits its choice in ascending position and ignores ``reverse``."""
+        from .matrix import Matrix
+
+        parent = self._parent
+        columnwise = _order(order) == "columnwise"
+        how = _how(how, _COMPACTIFY_HOWS)
+        desc = descriptor_lookup(transpose_first=columnwise)
+        if k is None:
+            width = _IndexOut("&k")
+            call("GxB_Matrix_compactify_width", [width, parent, desc])
+            k = width.value.value
+        k = _count(k)
+        dtype = UINT64 if asindex else parent.dtype
+        C = Matrix(dtype, k, parent._ncols, name=name) if columnwise else Matrix(dtype, parent._nrows, k, name=name)
+        call("GxB_Matrix_compactify", [C, parent, how, k, bool(reverse), bool(asindex), _seed(seed), desc])
+        return C
 
     def split(self, chunks, *, name=None):
         """GxB_Matrix_split (reference core/ss/matrix.py:281-339): a list of lists of Matrix

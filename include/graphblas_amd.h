@@ -363,6 +363,38 @@ GrB_Info GrB_Matrix_kronecker_Semiring(GrB_Matrix C, const GrB_Matrix Mask, cons
  * w(k) is the rank-k value of u and p(k) its original index, k < nvals(u). */
 GrB_Info GxB_Matrix_sort(GrB_Matrix C, GrB_Matrix P, GrB_BinaryOp op, const GrB_Matrix A, const GrB_Descriptor desc);
 GrB_Info GxB_Vector_sort(GrB_Vector w, GrB_Vector p, GrB_BinaryOp op, const GrB_Vector u, const GrB_Descriptor desc);
+/* selectk / compactify (reference core/ss/matrix.py:3815-3989, core/ss/vector.py:1407-1560): k
+ * entries of every row of A (every column under GrB_DESC_T0; a vector is one row).  A row's d
+ * entries have positions 0 .. d-1 in ascending column order; `how` puts them in an order s:
+ * FIRST by position, LAST by position reversed, SMALLEST ascending by (value, position) -- the
+ * order of GxB_Matrix_sort under GrB_LT of A's type, -0.0 equal to +0.0 --, LARGEST that order
+ * reversed (equal values in descending position), RANDOM ascending by (h(seed, row, position),
+ * position) with h a stateless 64-bit mixing hash, so that the first k are a uniform k-subset.
+ * selectk: C keeps s[0 .. min(k, d) - 1] of every row, each entry at its own column with its own
+ * value; C has A's shape and type, an iso A gives an iso C.
+ * compactify: row i of C holds m = min(k, d) entries at columns 0 .. m-1 (rows 0 .. m-1 of
+ * column j under T0), entry t the value at s[t], or with asindex the column index (row index
+ * under T0) of s[t] as GrB_UINT64; with reverse, that of s[m-1-t].  C is nrows x k, or k x ncols
+ * under T0 (a vector of size k).  RANDOM emits the chosen entries in ascending position and
+ * ignores reverse.  For an iso A, SMALLEST and LARGEST (in selectk too) and compactify's RANDOM
+ * without asindex are FIRST without reverse, as in the reference, and C is iso unless asindex is set.
+ * No mask, no accumulator: C is replaced and may be A.  An unknown `how` is GrB_INVALID_VALUE, a
+ * C of another shape GrB_DIMENSION_MISMATCH, a C whose type is neither A's nor (asindex)
+ * GrB_UINT64 GrB_DOMAIN_MISMATCH; on any error C is untouched.  GxB_Matrix_compactify_width
+ * returns the smallest k that loses nothing: the longest row (column under T0), 0 when empty. */
+typedef enum { GxB_SELECTK_FIRST, GxB_SELECTK_LAST, GxB_SELECTK_SMALLEST,
+               GxB_SELECTK_LARGEST, GxB_SELECTK_RANDOM } GxB_SelectK_How;
+GrB_Info GxB_Matrix_selectk(GrB_Matrix C, const GrB_Matrix A, int how, GrB_Index k,
+                            uint64_t seed, const GrB_Descriptor desc);
+GrB_Info GxB_Vector_selectk(GrB_Vector w, const GrB_Vector u, int how, GrB_Index k,
+                            uint64_t seed, const GrB_Descriptor desc);
+GrB_Info GxB_Matrix_compactify(GrB_Matrix C, const GrB_Matrix A, int how, GrB_Index k,
+                               bool reverse, bool asindex, uint64_t seed,
+                               const GrB_Descriptor desc);
+GrB_Info GxB_Vector_compactify(GrB_Vector w, const GrB_Vector u, int how, GrB_Index k,
+                               bool reverse, bool asindex, uint64_t seed,
+                               const GrB_Descriptor desc);
+GrB_Info GxB_Matrix_compactify_width(GrB_Index *k, const GrB_Matrix A, const GrB_Descriptor desc);
 /* eWiseUnion (reference core/matrix.py:2044-2161, core/vector.py:1141-1260): C<M> = accum(C, T),
  * T on the structure of A' union B' (after GrB_INP0 / GrB_INP1) with the type of add's result:
  * add(A'(i,j), B'(i,j)) where both are stored, add(A'(i,j), beta) where only A' is and
@@ -655,6 +687,10 @@ GrB_Info GxB_MatrixMarket_free(void *p);
  * the longest row of the sub-wave and of the workgroup class, which can only be lowered and
  * read back as their defaults while unset).  get_int also reads "stat_sort_rows_wave" /
  * "stat_sort_rows_block" / "stat_sort_rows_long" (rows each class took in the last sort),
+ * "selectk_wave_max" / "selectk_block_max" (the same two bounds for the value and random modes
+ * of selectk / compactify) and "stat_selectk_rows_all" / "_wave" / "_block" / "_long" (rows the
+ * last such matrix call kept whole because they have at most k entries, and rows of two or more
+ * entries each class ranked),
  * "stat_union_both" / "stat_union_a_only" / "stat_union_b_only" (entries of T the last
  * eWiseUnion computed from both operands, from A' and beta, from alpha and B'),
  * "stat_concat_bitmap" / "stat_split_bitmap" (1 when the last concat / split moved bitmaps, 0
