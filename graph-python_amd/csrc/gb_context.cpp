@@ -420,6 +420,7 @@ int64_t gb_read_i64(const int64_t *dptr) {
 }
 
 int64_t gb_iso_ts_dump();  // gb_spmv_iso.hip (diagnostics)
+int64_t gb_iso_push_launches();  // gb_spmv_iso.hip: launches of the BFS kernel that pushed
 
 static const char *k_type_names[] = {"BOOL", "INT8", "UINT8", "INT16", "UINT16", "INT32",
                                      "UINT32", "INT64", "UINT64", "FP32", "FP64"};
@@ -523,6 +524,9 @@ GrB_Info GxB_Global_get_int(const char *key, int64_t *value) {
     // statistics (read-only): BFS level speculation (gb_bfs_loop.hip)
     if (gb_deferred_stat(key, value)) return GrB_SUCCESS;
     // vector counts read with a device copy (stream sync) instead of the kernel's mailbox
+    if (!strcmp(key, "stat_iso_push_launches")) {  // device count of pushing BFS launches (syncs)
+        return gb_api(nullptr, [&] { *value = gb_iso_push_launches(); });
+    }
     if (!strcmp(key, "stat_spmv_host_push")) {
         *value = g_stat_host_push.load(std::memory_order_relaxed);
         return GrB_SUCCESS;

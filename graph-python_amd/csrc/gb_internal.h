@@ -391,7 +391,8 @@ struct gb_csr_view {
     const void *vals = nullptr;
     bool iso = false;
     int tcode = 0;
-    // hub chunks (rows longer than hub_H cut into hub_H-edge pieces): pairs (row, piece)
+    // hub chunks (rows longer than hub_H cut into hub_H-edge pieces): pairs (row, piece), then
+    // the sections of gb_hub_sections_of (a record per piece, every row's length)
     const int32_t *hubs = nullptr;
     int64_t nhubs = 0, hub_H = 0;
     const uint64_t *nonempty = nullptr;  // bitmap of rows with entries (when attached)
@@ -409,6 +410,31 @@ struct gb_csr_view {
     gb_scratch own;
 };
 void gb_get_csr(gb_csr_view &v, GB_Obj *A);
+// The hub table's allocation goes on after its nhubs (row, piece) pairs (and the spare ints
+// that follow them) with two sections, built and freed with it: one 16-byte record per piece
+// -- its row, its entry count and its first entry position, so the lane that tests a piece
+// reads one line and a hit goes to its columns without reading the row's bounds -- and every
+// row's length as 32 bits (exact: a row has fewer than 2^31 entries), one read per vertex for
+// the next-frontier hint instead of two row pointers.
+struct gb_hub_piece {
+    int32_t row;  // the piece's row
+    int32_t len;  // its entries (hub_H, or fewer for a row's last piece)
+    int64_t pos;  // its first entry
+};
+static_assert(sizeof(gb_hub_piece) == 16, "one 16-byte load per piece");
+struct gb_hub_sections {
+    const gb_hub_piece *piece = nullptr;  // nhubs records
+    const uint32_t *rowlen = nullptr;     // nrows: entries of each row
+};
+// ints before the records: the pairs and two spare ints, rounded up to 16 bytes
+__host__ __device__ inline int64_t gb_hub_prefix_ints(int64_t nhubs) { return (2 * nhubs + 2 + 3) & ~(int64_t)3; }
+__host__ __device__ inline gb_hub_sections gb_hub_sections_of(const int32_t *tab, int64_t nhubs) {
+    gb_hub_sections s;
+    s.piece = reinterpret_cast<const gb_hub_piece *>(tab + gb_hub_prefix_ints(nhubs));
+    s.rowlen = reinterpret_cast<const uint32_t *>(s.piece + nhubs);
+    return s;
+}
+inline int64_t gb_hub_table_ints(int64_t nhubs, int64_t nrows) { return gb_hub_prefix_ints(nhubs) + 4 * nhubs + nrows; }
 // attach the cached hub-chunk table of matrix A's orientation (0 CSR, 1 CSC) to v
 void gb_view_hubs(gb_csr_view &v, GB_Obj *A, int orient, int64_t H);
 // attach the cached non-empty-rows bitmap of matrix A's orientation, and its rank prefix, to v

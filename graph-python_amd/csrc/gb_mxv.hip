@@ -518,19 +518,32 @@ __global__ void k_hub_count(const int64_t *__restrict__ rowptr, int64_t n, int64
         cnt[r] = d > thresh ? (d + H - 1) / H : 0;
     }
 }
+// rec (nullptr: not kept): a record per piece -- row, entry count, first entry position
 __global__ void k_hub_fill(const int64_t *__restrict__ cnt, const int64_t *__restrict__ off, int64_t n,
-                           int32_t *__restrict__ tab) {
+                           int32_t *__restrict__ tab, const int64_t *__restrict__ rowptr, int64_t H,
+                           gb_hub_piece *__restrict__ rec) {
     for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
         const int64_t c = cnt[r], o = off[r];
         for (int64_t i = 0; i < c; i++) {
             tab[2 * (o + i)] = (int32_t)r;
             tab[2 * (o + i) + 1] = (int32_t)i;
+            if (rec) {
+                const int64_t p0 = rowptr[r] + i * H, left = rowptr[r + 1] - p0;
+                rec[o + i] = gb_hub_piece{(int32_t)r, (int32_t)(left < H ? left : H), p0};
+            }
         }
     }
 }
+__global__ void k_row_len_u32(const int64_t *__restrict__ rowptr, int64_t n, uint32_t *__restrict__ out) {
+    GB_GRID_LOOP(r, n)
+        out[r] = (uint32_t)(rowptr[r + 1] - rowptr[r]);
+}
 
-// (row, piece) table of the rows of v longer than thresh, cut into H-entry pieces
-static int32_t *gb_build_chunk_table(const gb_csr_view &v, int64_t thresh, int64_t H, int64_t *total_out) {
+// (row, piece) table of the rows of v longer than thresh, cut into H-entry pieces.  sections:
+// the allocation goes on after the pairs with a record per piece and every row's length
+// (gb_hub_sections_of, gb_internal.h) -- the hub table of the BFS push
+static int32_t *gb_build_chunk_table(const gb_csr_view &v, int64_t thresh, int64_t H, int64_t *total_out,
+                                     bool sections = false) {
     const int64_t n = v.nrows;
     gb_scratch s;
     int64_t *cnt = s.get<int64_t>(n + 1);
@@ -540,9 +553,16 @@ static int32_t *gb_build_chunk_table(const gb_csr_view &v, int64_t thresh, int64
     GB_LAUNCH_CHECK();
     gb_exclusive_scan_i64(cnt, off, n);
     const int64_t total = gb_read_i64(off + n);
-    int32_t *tab = gb_malloc_n<int32_t>(2 * total + 2);
-    hipLaunchKernelGGL(k_hub_fill, dim3(g), dim3(256), 0, gb_stream(), cnt, off, n, tab);
+    int32_t *tab = gb_malloc_n<int32_t>(sections ? gb_hub_table_ints(total, n) : 2 * total + 2);
+    const gb_hub_sections sec = sections ? gb_hub_sections_of(tab, total) : gb_hub_sections{};
+    hipLaunchKernelGGL(k_hub_fill, dim3(g), dim3(256), 0, gb_stream(), cnt, off, n, tab, v.rowptr, H,
+                       const_cast<gb_hub_piece *>(sec.piece));
     GB_LAUNCH_CHECK();
+    if (sections) {
+        hipLaunchKernelGGL(k_row_len_u32, dim3(g), dim3(256), 0, gb_stream(), v.rowptr, n,
+                           const_cast<uint32_t *>(sec.rowlen));
+        GB_LAUNCH_CHECK();
+    }
     *total_out = total;
     return tab;
 }
@@ -566,7 +586,7 @@ void gb_view_hubs(gb_csr_view &v, GB_Obj *A, int orient, int64_t H) {
     if (!c.hub_tab || c.hub_H != H) {
         gb_stat_add("hub_tables_built", 1);
         gb_free(c.hub_tab);
-        c.hub_tab = gb_build_chunk_table(v, H, H, &c.hub_n);
+        c.hub_tab = gb_build_chunk_table(v, H, H, &c.hub_n, true);
         c.hub_H = H;
         // the longest row, for host-side direction decisions on small frontiers (gb_spmv_iso)
         gb_scratch s;

@@ -26,10 +26,19 @@
 #include "gb_dispatch.cuh"
 #include "gb_internal.h"
 
-// Direction state words (gb_state.h, GB_DIR_STATE_OFFSET; zero between calls
+// Direction state words (gb_state.h, GB_DIR_STATE_OFFSET; ST_PUSHES apart, zero between calls
 // except ST_PUSH, which every prep rewrites):
 //   [ST_PUSH]     chosen direction: 1 push, 0 pull (written by the last prep block)
-enum { ST_PUSH = 0 };
+//   [ST_PUSHES]   launches of k_iso_work that pushed, since the process began (a running
+//                 count, never reset: GxB_Global_get_int "stat_iso_push_launches" -- what the
+//                 device chose is not otherwise visible to the host, the results being the same)
+enum { ST_PUSH = 0, ST_PUSHES = 1 };
+int64_t gb_iso_push_launches() {
+    unsigned long long c = 0;
+    GB_HIP(hipStreamSynchronize(gb_stream()));
+    GB_HIP(hipMemcpy(&c, gb_device_state() + GB_DIR_STATE_OFFSET + ST_PUSHES, sizeof(c), hipMemcpyDeviceToHost));
+    return (int64_t)c;
+}
 #define PULL_U 4  // bitmap words per wave step (independent loads in flight)
 
 struct gb_dir_rule {
@@ -98,55 +107,83 @@ __global__ __launch_bounds__(SPMV_BLOCK) void k_dir_prep(
     if (gb_grid_sum(mf, gst, &total)) dst[ST_PUSH] = gb_dir_decide(total, rule) ? 1ULL : 0ULL;
 }
 
-// set the output bits of up to 4 targets per lane (unmasked, not yet set);
-// returns how many bits this lane turned on
-__device__ __forceinline__ long long gb_push_targets(const int32_t (&j)[4], bool (&ok)[4],
+// set the output bits of up to W targets per lane (unmasked, not yet set);
+// returns how many bits this lane turned on.  hlen (nullptr: no hint): the row lengths the
+// next-frontier hint sums over the added vertices (gb_hub_sections::rowlen), read after the
+// atomics, all at once
+template <int W>
+__device__ __forceinline__ long long gb_push_targets(const int32_t (&j)[W], bool (&ok)[W],
                                                      const uint64_t *__restrict__ mbits, bool mcomp,
                                                      unsigned long long *__restrict__ tbits,
-                                                     const int64_t *__restrict__ hprow, long long &mfn,
+                                                     const uint32_t *__restrict__ hlen, long long &mfn,
                                                      const uint64_t *__restrict__ qbits, bool serial = false,
                                                      int64_t qroot = -1) {
-    unsigned long long cur[4];
+    uint32_t cur[W];  // the 32-bit half of the output word that holds the target's bit
+    const uint32_t *t32 = reinterpret_cast<const uint32_t *>(tbits);
     if (serial) {  // diagnostics (iso_dbg 128): the round-4 order, each read behind the one before
         if (mbits) {
 #pragma unroll
-            for (int u = 0; u < 4; u++)
+            for (int u = 0; u < W; u++)
                 if (ok[u]) ok[u] = (gb_bit(mbits, j[u]) || (qbits && gb_bit(qbits, j[u]))) != mcomp;
         }
 #pragma unroll
-        for (int u = 0; u < 4; u++) cur[u] = ok[u] ? tbits[j[u] >> 6] : ~0ULL;
+        for (int u = 0; u < W; u++) cur[u] = ok[u] ? t32[j[u] >> 5] : ~0u;
     } else {
-        // the mask words (w's and the fused stamp's q) and the output word of every target
-        // are read at once: one round trip instead of three dependent ones
-        uint64_t mw[4], qw[4];
+        // the mask words (w's and the fused stamp's q) and the output word of every target are
+        // read at once: one round trip instead of three dependent ones.  Only the halves that
+        // hold the targets' bits are read (half the registers)
+        const uint32_t *m32 = reinterpret_cast<const uint32_t *>(mbits);
+        const uint32_t *q32 = reinterpret_cast<const uint32_t *>(qbits);
+        uint32_t mw[W], qw[W];
 #pragma unroll
-        for (int u = 0; u < 4; u++) {
+        for (int u = 0; u < W; u++) {
             mw[u] = qw[u] = 0;
-            cur[u] = ~0ULL;
+            cur[u] = ~0u;
             if (ok[u]) {
-                if (mbits) mw[u] = mbits[j[u] >> 6];
-                if (mbits && qbits) qw[u] = qbits[j[u] >> 6];
-                cur[u] = tbits[j[u] >> 6];
+                if (mbits) mw[u] = m32[j[u] >> 5];
+                if (mbits && qbits) qw[u] = q32[j[u] >> 5];
+                cur[u] = t32[j[u] >> 5];
             }
         }
         if (mbits) {
             // qroot: the fused stamp's frontier is one pending vertex (gb_push_root), not q's bits
 #pragma unroll
-            for (int u = 0; u < 4; u++)
-                if (ok[u]) ok[u] = (((((mw[u] | qw[u]) >> (j[u] & 63)) & 1ULL) != 0) || j[u] == qroot) != mcomp;
+            for (int u = 0; u < W; u++)
+                if (ok[u]) ok[u] = (((((mw[u] | qw[u]) >> (j[u] & 31)) & 1u) != 0) || j[u] == qroot) != mcomp;
         }
     }
+    // every atomic of the step is issued before the first result is looked at (a result tested
+    // where its atomic is issued makes each one wait for the one before: W round trips).  The
+    // atomics too go to the 32-bit halves; within a launch nothing else writes the output words
+    unsigned int *t32w = reinterpret_cast<unsigned int *>(tbits);
+    uint32_t old[W];
+    bool won[W];  // first: the atomic is tried
+    // (the words read above are all tested before the first atomic: a read's result used
+    // between two atomics under conditions waits for the atomic before it too.  old starts as
+    // that word, not a constant: the compiler moves a test of "constant or the atomic's
+    // result" up to the atomic, and its wait with it)
+#pragma unroll
+    for (int u = 0; u < W; u++) {
+        old[u] = cur[u];
+        won[u] = ok[u] && !((cur[u] >> (j[u] & 31)) & 1u);
+    }
+#pragma unroll
+    for (int u = 0; u < W; u++)
+        if (won[u]) old[u] = atomicOr(&t32w[j[u] >> 5], 1u << (j[u] & 31));
+#pragma unroll
+    for (int u = 0; u < W; u++) won[u] = won[u] && !((old[u] >> (j[u] & 31)) & 1u);
     long long added = 0;
 #pragma unroll
-    for (int u = 0; u < 4; u++) {
-        const unsigned long long m = 1ULL << (j[u] & 63);
-        if (ok[u] && !(cur[u] & m)) {
-            const unsigned long long old = atomicOr(&tbits[j[u] >> 6], m);
-            if (!(old & m)) {
-                added++;
-                if (hprow) mfn += hprow[j[u] + 1] - hprow[j[u]];  // edges of the next frontier
-            }
-        }
+    for (int u = 0; u < W; u++) added += won[u] ? 1 : 0;
+    // edges of the next frontier
+    if (hlen) {
+        // (every lane reads, element 0 where nothing was added: the sum of "0 or a load under
+        // a condition" is moved up to the load by the compiler, and each load then waited for)
+        uint32_t dl[W];
+#pragma unroll
+        for (int u = 0; u < W; u++) dl[u] = hlen[won[u] ? j[u] : 0];
+#pragma unroll
+        for (int u = 0; u < W; u++) mfn += won[u] ? dl[u] : 0u;
     }
     return added;
 }
@@ -278,16 +315,19 @@ __device__ __forceinline__ long long gb_asg_words(const gb_asg_dev &g, int64_t w
 }
 
 // Push (top-down).  First the matrix's hub chunks (rows longer than H cut into
-// H-edge pieces, a static table; a wave tests 16 strided entries against the
-// frontier at once and expands the hits, 256 edges a step).  Then the frontier
-// words, 4 per wave step: the rows of their frontier vertices (at most H edges
-// each) go into the wave's segment list and are walked as one edge stream.
+// H-edge pieces, a static table that holds each piece's row and bounds; a wave
+// tests 16 strided entries against the frontier at once and expands the hits,
+// 512 edges a step).  Then the frontier words, 4 per wave step: the rows of
+// their frontier vertices (at most H edges each) go into the wave's segment
+// list and are walked as one edge stream.  The row bounds of the first step's
+// vertices (and the fused stamp's word) are read in the round trip of the hub
+// entries' frontier-bit probes, not after the hub pieces.
 __device__ __forceinline__ long long gb_push_phase(int64_t nwords_u, const uint64_t *__restrict__ ubits,
                                                   const int64_t *__restrict__ prow, const int32_t *__restrict__ pcol,
                                                   const int32_t *__restrict__ hubs, int64_t nhubs, int64_t H,
                                                   const uint64_t *__restrict__ mbits, bool mcomp,
                                                   unsigned long long *__restrict__ tbits, gb_wlist &L,
-                                                  const int64_t *__restrict__ hprow, long long &mfn,
+                                                  const uint32_t *__restrict__ hlen, long long &mfn,
                                                   const uint64_t *__restrict__ qbits, const gb_asg_dev &g,
                                                   long long &adelta, bool serial = false, bool prefetch = true,
                                                   bool defer = false) {
@@ -295,6 +335,7 @@ __device__ __forceinline__ long long gb_push_phase(int64_t nwords_u, const uint6
     const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     const unsigned long long lt = (1ULL << lane) - 1;
+    const gb_hub_sections sec = gb_hub_sections_of(hubs, nhubs);
     long long added = 0;
     // the frontier words of this wave's first 16 steps, loaded before the hub chunks (round 5):
     // lane l holds step l / 4's word l % 4, so a small frontier's scan costs one load round trip
@@ -305,37 +346,42 @@ __device__ __forceinline__ long long gb_push_phase(int64_t nwords_u, const uint6
         const int64_t wl = wave * 4 + (int64_t)(lane >> 2) * nwaves * 4 + (lane & 3);
         if (wl < nwords_u) pre = ubits[wl];
     }
-    // hub chunks: lane l of wave w tests table entry w + l * nwaves (a hub's
-    // consecutive chunks land on different waves); hits are expanded in turn
-    for (int64_t base = wave; base < nhubs; base += nwaves * 16) {
+    // hub chunks: lane l of wave w tests table entry w + l * nwaves (a hub's consecutive
+    // chunks land on different waves).  An entry's row and its piece's bounds come in one
+    // round trip -- the first sweep's with the frontier words above
+    int hk = -1, hl = 0;  // the tested piece's row (-1: none) and length
+    int64_t hp = 0;        // its first edge
+    uint64_t hw;  // the frontier word of the entry's row
+    auto hub_entry = [&](int64_t base) {
         const int64_t h = base + (int64_t)lane * nwaves;
-        int k = 0, cc = 0;
-        bool act = false;
+        hk = -1;
         if (lane < 16 && h < nhubs) {
-            k = hubs[2 * h];
-            cc = hubs[2 * h + 1];
-            act = gb_bit(ubits, k);
+            const gb_hub_piece pc = sec.piece[h];  // one 16-byte load
+            hk = pc.row;
+            hl = pc.len;
+            hp = pc.pos;
         }
-        unsigned long long b = __ballot(act);
-        while (b) {
-            const int l = __ffsll(b) - 1;
-            b &= b - 1;
-            const int64_t kk = __shfl(k, l, 64);
-            const int64_t c = __shfl(cc, l, 64);
-            const int64_t p0 = prow[kk] + c * H, pe = prow[kk + 1];
-            const int64_t p1 = (p0 + H < pe) ? p0 + H : pe;
-            for (int64_t p = p0 + lane; p < p1; p += 256) {
-                int32_t j[4];
-                bool ok[4];
+    };
+    if (wave < nhubs) hub_entry(wave);
+    // one step's frontier rows: their bounds and the fused stamp's word, all loads at once ...
+    auto rows_load = [&](int64_t w0, uint64_t mine, int64_t (&p0)[4], int64_t (&d)[4], uint64_t &cw) {
+        const int64_t wl = w0 + (lane & 3);
+        cw = 0;
+        if (qbits && lane < 4 && wl < nwords_u && mine) cw = g.bits[wl];
+        int64_t p1[4];  // the lengths are taken after the last load is issued, or each load waits
 #pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    ok[u] = p + 64 * u < p1;
-                    j[u] = ok[u] ? pcol[p + 64 * u] : 0;
-                }
-                added += gb_push_targets(j, ok, mbits, mcomp, tbits, hprow, mfn, qbits, serial);
+        for (int u = 0; u < 4; u++) {
+            const uint64_t word = __shfl(mine, u, 64);
+            p0[u] = p1[u] = 0;
+            if ((word >> lane) & 1ULL) {
+                const int64_t k = ((w0 + u) << 6) + lane;
+                p0[u] = prow[k];
+                p1[u] = prow[k + 1];
             }
         }
-    }
+#pragma unroll
+        for (int u = 0; u < 4; u++) d[u] = p1[u] - p0[u];
+    };
     // the wave's segment list walked as one edge stream, then emptied
     int n = 0;
     auto flush = [&]() {
@@ -354,37 +400,14 @@ __device__ __forceinline__ long long gb_push_phase(int64_t nwords_u, const uint6
                     j[u] = pcol[L.p[s] + (e - gb_wlist_start(L, s))];
                 }
             }
-            added += gb_push_targets(j, ok, mbits, mcomp, tbits, hprow, mfn, qbits, serial);
+            added += gb_push_targets<4>(j, ok, mbits, mcomp, tbits, hlen, mfn, qbits, serial);
         }
         gb_wave_sync();
         n = 0;
     };
-    // frontier words, 4 per wave step (lanes 0-3 load them; the first 16 steps' came above).
-    // defer (knob iso_pack): the rows of successive steps pile up in the list, which is walked
-    // only when the next step's rows would not fit or the words are exhausted -- one chain of
-    // edge / mask / output reads for a sparse frontier's few rows per step instead of one per step
-    int step = 0;
-    for (int64_t w0 = wave * 4; w0 < nwords_u; w0 += nwaves * 4, step++) {
-        const int64_t wl = w0 + (lane & 3);
-        uint64_t mine;
-        if (prefetch && step < 16) {
-            mine = __shfl(pre, (step << 2) | (lane & 3), 64);
-        } else {
-            mine = wl < nwords_u ? ubits[wl] : 0;
-        }
-        if (!__ballot(mine != 0)) continue;
-        if (qbits) adelta += gb_asg_words(g, w0, nwords_u, mine, lane);
-        int64_t p0[4], d[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const uint64_t word = __shfl(mine, u, 64);
-            p0[u] = d[u] = 0;
-            if ((word >> lane) & 1ULL) {
-                const int64_t k = ((w0 + u) << 6) + lane;
-                p0[u] = prow[k];
-                d[u] = prow[k + 1] - p0[u];
-            }
-        }
+    // ... then the stamp of the step's words, and its rows (hubs apart) appended to the list
+    auto rows_add = [&](int64_t w0, uint64_t mine, const int64_t (&p0)[4], const int64_t (&d)[4], uint64_t cw) {
+        if (qbits) adelta += gb_asg_words(g, w0, nwords_u, mine, lane, &cw);
         unsigned long long bb[4];
         int add = 0;
 #pragma unroll
@@ -392,7 +415,7 @@ __device__ __forceinline__ long long gb_push_phase(int64_t nwords_u, const uint6
             bb[u] = __ballot(d[u] > 0 && d[u] <= H);  // hubs: done by their chunks
             add += __popcll(bb[u]);
         }
-        if (!add) continue;
+        if (!add) return;
         if (n + add > WL_MAX) flush();  // a step has at most 256 rows: it fits an empty list
 #pragma unroll
         for (int u = 0; u < 4; u++) {
@@ -403,7 +426,77 @@ __device__ __forceinline__ long long gb_push_phase(int64_t nwords_u, const uint6
             }
             n += __popcll(bb[u]);
         }
-        if (!defer) flush();
+    };
+    // the first sweep's frontier-bit probes go out with the bounds of the first step's rows
+    // (every lane reads a word, word 0 without an entry: a load under a condition whose result
+    // is tested at once is waited for where it is issued)
+    int step = 0;
+    int64_t w0 = wave * 4;
+    bool act;
+    {
+        const bool first = prefetch && w0 < nwords_u;
+        const uint64_t mine = first ? __shfl(pre, lane & 3, 64) : 0;
+        int64_t p0[4], d[4];
+        uint64_t cw;
+        const bool any = __ballot(mine != 0) != 0;
+        // (the probe is issued after the wait for the frontier words: issued before it, that
+        // wait -- which cannot tell how many loads under conditions are in flight -- would
+        // take the probe in, and the rows' bounds would go out a round trip later)
+        __builtin_amdgcn_sched_barrier(0);
+        hw = ubits[(hk >= 0 ? hk : 0) >> 6];
+        if (any) rows_load(w0, mine, p0, d, cw);
+        act = hk >= 0 && ((hw >> (hk & 63)) & 1ULL);
+        if (any) rows_add(w0, mine, p0, d, cw);
+        if (first) {
+            step = 1;
+            w0 += nwaves * 4;
+        }
+    }
+    // hits are expanded in turn, 512 edges a step: 8 columns per lane, then all the targets'
+    // words, then the atomics
+    for (int64_t base = wave; base < nhubs;) {
+        unsigned long long b = __ballot(act);
+        while (b) {
+            const int l = __ffsll(b) - 1;
+            b &= b - 1;
+            const int64_t pp = __shfl(hp, l, 64);
+            const int ln = __shfl(hl, l, 64);
+            for (int e0 = lane; e0 < ln; e0 += 512) {
+                int32_t j[8];
+                bool ok[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    ok[u] = e0 + 64 * u < ln;
+                    j[u] = ok[u] ? pcol[pp + e0 + 64 * u] : 0;
+                }
+                added += gb_push_targets<8>(j, ok, mbits, mcomp, tbits, hlen, mfn, qbits, serial);
+            }
+        }
+        base += nwaves * 16;
+        if (base >= nhubs) break;
+        hub_entry(base);
+        hw = ubits[(hk >= 0 ? hk : 0) >> 6];
+        act = hk >= 0 && ((hw >> (hk & 63)) & 1ULL);
+    }
+    if (n && !defer) flush();
+    // frontier words, 4 per wave step (lanes 0-3 load them; the first 16 steps' came above).
+    // defer (knob iso_pack): the rows of successive steps pile up in the list, which is walked
+    // only when the next step's rows would not fit or the words are exhausted -- one chain of
+    // edge / mask / output reads for a sparse frontier's few rows per step instead of one per step
+    for (; w0 < nwords_u; w0 += nwaves * 4, step++) {
+        const int64_t wl = w0 + (lane & 3);
+        uint64_t mine;
+        if (prefetch && step < 16) {
+            mine = __shfl(pre, (step << 2) | (lane & 3), 64);
+        } else {
+            mine = wl < nwords_u ? ubits[wl] : 0;
+        }
+        if (!__ballot(mine != 0)) continue;
+        int64_t p0[4], d[4];
+        uint64_t cw;
+        rows_load(w0, mine, p0, d, cw);
+        rows_add(w0, mine, p0, d, cw);
+        if (n && !defer) flush();
     }
     if (n) flush();
     return added;
@@ -418,8 +511,8 @@ __device__ __forceinline__ long long gb_push_root(int64_t root, const int64_t *_
                                                  const int32_t *__restrict__ pcol,
                                                  const uint64_t *__restrict__ mbits, bool mcomp,
                                                  unsigned long long *__restrict__ tbits,
-                                                 const int64_t *__restrict__ hprow, long long &mfn, bool stamp,
-                                                 const gb_asg_dev &g, long long &adelta) {
+                                                 const uint32_t *__restrict__ hlen, long long &mfn,
+                                                 bool stamp, const gb_asg_dev &g, long long &adelta) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -439,7 +532,7 @@ __device__ __forceinline__ long long gb_push_root(int64_t root, const int64_t *_
             ok[u] = p + 64 * u < p1;
             j[u] = ok[u] ? pcol[p + 64 * u] : 0;
         }
-        added += gb_push_targets(j, ok, mbits, mcomp, tbits, hprow, mfn, nullptr, false, stamp ? root : -1);
+        added += gb_push_targets<4>(j, ok, mbits, mcomp, tbits, hlen, mfn, nullptr, false, stamp ? root : -1);
     }
     return added;
 }
@@ -1103,15 +1196,20 @@ __global__ __launch_bounds__(SPMV_BLOCK) void k_iso_work(
     const uint64_t *qbits = nullptr;
     if (a.asg.bits && (!a.asg_qiso || gb_dyn_nonzero(a.asg_qiso, a.asg_qiso_code))) qbits = ubits;
     long long mfn = 0, cnt = 0, adelta = 0;
+    if ((a.root >= 0 || push) && blockIdx.x == 0 && threadIdx.x == 0)
+        atomicAdd(gst + GB_DIR_STATE_OFFSET + ST_PUSHES, 1ULL);  // result unused: nothing waits for it
+    // push: the hint's row lengths (the hub table's section; hprow is the push orientation's
+    // row pointers)
+    const uint32_t *hlen = (a.hprow && hubs) ? gb_hub_sections_of(hubs, nhubs).rowlen : nullptr;
     if (a.dbg & 4)
         ;
     else if (a.root >= 0)
-        cnt = gb_push_root(a.root, prow, pcol, mbits, mcomp, (unsigned long long *)tbits, a.hprow, mfn,
+        cnt = gb_push_root(a.root, prow, pcol, mbits, mcomp, (unsigned long long *)tbits, hlen, mfn,
                            a.asg.bits != nullptr, a.asg, adelta);
     else if (push)
         cnt = gb_push_phase(nwords_u, ubits, prow, pcol, hubs, nhubs, H, mbits, mcomp,
-                            (unsigned long long *)tbits, L, a.hprow, mfn, qbits, a.asg, adelta, (a.dbg & 128) != 0,
-                            (a.dbg & 512) == 0, (a.pack & 2) != 0);
+                            (unsigned long long *)tbits, L, hlen, mfn, qbits, a.asg, adelta,
+                            (a.dbg & 128) != 0, (a.dbg & 512) == 0, (a.pack & 2) != 0);
     else {
         // the heads are found through the non-empty bitmap's ranks: without it, no heads
         const int32_t *ph =

@@ -1,5 +1,6 @@
 // gb_state.h -- layout of the persistent device state words (zeroed once per
-// process by gb_device_state(); every user leaves its words as it found them).
+// process by gb_device_state(); every user leaves its words as it found them,
+// but for the running count of pushing BFS launches in the direction state).
 #pragma once
 
 #define GB_GRID_SHARDS 32

@@ -1,8 +1,10 @@
 """A/B timing of the headline BFS loop (bench.py's notebook loop, any_pair, R-MAT s22, 16
 roots) under several library-knob settings, interleaved in one process so box-to-box and
 drift noise cancel.  usage: python3 tools/ab_bfs.py SCALE ROUNDS "k=v,k=v" "k=v" ...
-("" = defaults).  Prints per setting: median and min ms per BFS over the rounds, and the
-per-level minimum event-bracketed SpMV time of root 7.  Diagnostic, GPU box."""
+("" = defaults).  Prints per setting: median and min ms per BFS over the rounds, the
+per-level minimum event-bracketed SpMV time of root 7, and each root's minimum wall time (us)
+over the rounds.  The library is the tree's, or the one GRAPHBLAS_AMD_LIB names (a parent
+build, for runs of both in one call).  Diagnostic, GPU box."""
 import ctypes
 import os
 import sys
@@ -75,6 +77,7 @@ def bfs(src, ev=None):
 
 
 res = {s: [] for s in settings}
+per_root = {s: [] for s in settings}
 lev = {s: [] for s in settings}
 for s in settings:  # warm-up (builds the caches of each setting)
     apply(s)
@@ -86,9 +89,12 @@ for rnd in range(rounds):
     for s in settings:
         apply(s)
         t0 = time.perf_counter()
+        marks = [t0]
         for r in roots:
             bfs(r)
-        res[s].append((time.perf_counter() - t0) / len(roots) * 1e3)
+            marks.append(time.perf_counter())
+        res[s].append((marks[-1] - t0) / len(roots) * 1e3)
+        per_root[s].append(np.diff(marks) * 1e6)
         ev = []
         bfs(roots[7], ev)
         torch.cuda.synchronize()
@@ -99,3 +105,5 @@ for s in settings:
     per = np.array(lev[s]).min(axis=0)
     print(f"[{s or 'defaults'}] ms/BFS median {np.median(t):.4f} min {t.min():.4f} max {t.max():.4f} | root7 levels us "
           + " ".join(f"{x:.1f}" for x in per), flush=True)
+    print(f"[{s or 'defaults'}] per root us (min of rounds) "
+          + " ".join(f"{x:.1f}" for x in np.array(per_root[s]).min(axis=0)), flush=True)
