@@ -539,10 +539,12 @@ GrB_Info GxB_Global_get_int(const char *key, int64_t *value) {
         return gb_api(nullptr, [&] { *value = gb_iso_ts_dump(); });
     }
     // the sort's per-class row counts (read from the device here, not by the sort) and the
-    // defaults of its class bounds (gb_sort.hip)
+    // defaults of its class bounds (gb_sort.hip); the same of selectk / compactify and of scan
     {
         bool mine = false;
-        const GrB_Info info = gb_api(nullptr, [&] { mine = gb_sort_stat(key, value) || gb_selectk_stat(key, value); });
+        const GrB_Info info = gb_api(nullptr, [&] {
+            mine = gb_sort_stat(key, value) || gb_selectk_stat(key, value) || gb_scan_stat(key, value);
+        });
         if (mine || info != GrB_SUCCESS) return info;
     }
     // named kernel-class counters (gb_stat_add): "stat_" + name; 0 before the first count

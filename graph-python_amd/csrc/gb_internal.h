@@ -719,6 +719,11 @@ unsigned gb_sort_grid(int64_t items, int64_t per_block);
 // "stat_selectk_rows_{all,wave,block,long}" and the defaults of "selectk_wave_max" / "selectk_block_max"
 bool gb_selectk_stat(const char *key, int64_t *value);
 
+// scan (gb_scan.hip): the entry points are GxB_Matrix_scan / GxB_Vector_scan; GxB_Global_get_int
+// asks here for "stat_scan_rows_{wave,block,long}" (rows of two or more entries each class took in
+// the last call) and the defaults of "scan_wave_max" / "scan_block_max" / "scan_chunk"
+bool gb_scan_stat(const char *key, int64_t *value);
+
 // hash Gustavson C = A*B (gb_spgemm_hash.hip): flops = per-row product counts
 void gb_spgemm_hash(gb_mat_result &T, gb_csr_view &A, gb_csr_view &B, GrB_Semiring sr, bool iso,
                     const void *av, const void *bv, const int64_t *flops);

@@ -70,6 +70,7 @@ _SIGS = {
     "GxB_Matrix_compactify": [P, P, E, I, ctypes.c_bool, ctypes.c_bool, U, P],
     "GxB_Vector_compactify": [P, P, E, I, ctypes.c_bool, ctypes.c_bool, U, P],
     "GxB_Matrix_compactify_width": [P, P, P],
+    "GxB_Matrix_scan": [P] * 4, "GxB_Vector_scan": [P] * 4,
     "GxB_Matrix_eWiseUnion": [P] * 9, "GxB_Vector_eWiseUnion": [P] * 9,
     "GxB_Matrix_concat": [P, P, I, I, P], "GxB_Matrix_split": [P, I, I, P, P, P, P],
     "GrB_Matrix_diag": [P, P, L], "GxB_Matrix_diag": [P, P, L, P], "GxB_Vector_diag": [P, P, L, P],

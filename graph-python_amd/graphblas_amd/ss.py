@@ -1,14 +1,18 @@
 """``Vector.ss`` / ``Matrix.ss`` extension namespaces: the prefix scan, sort, split and concat.
 
-``prefix_scan`` restates reference core/ss/prefix_scan.py:12-172: a
+``scan`` is one call of GxB_Matrix_scan / GxB_Vector_scan (csrc/gb_scan.hip): a segmented
+inclusive scan of every row (column, vector) under a monoid, in the monoid's type; nothing goes
+through the host.  Its association order (include/graphblas_amd.h) is that of ``prefix_scan``
+below, so both return the same bits, floats included.
+
+``prefix_scan`` is the recipe ``scan`` replaced, kept as a public function and as the parity
+check of the device call.  It restates reference core/ss/prefix_scan.py:12-172: a
 Blelloch up-sweep / down-sweep expressed entirely as masked, accumulated
 ``mxm`` / ``vxm`` calls with the semiring ``<monoid>_first`` against small
 iso selection matrices (one per level, log2(N) levels), on the entries of
-each row compacted to positions 0..deg-1.  Every level is one library call,
-so the scan runs on the device kernels of the hot path (masked SpGEMM /
-SpMV + accumulate write-back).  Compaction / de-compaction of the index
-space goes through to_coo / from_coo (the reference uses the ss export /
-import of the same arrays).
+each row compacted to positions 0..deg-1.  Every level is one library call;
+compaction / de-compaction of the index space goes through to_coo / from_coo
+(the reference uses the ss export / import of the same arrays).
 
 ``sort`` is one call of GxB_Matrix_sort / GxB_Vector_sort (csrc/gb_sort.hip): a
 segmented sort on the device, nothing goes through the host.  The k largest
@@ -491,13 +495,46 @@ class _IndexOut:
         return ctypes.byref(self.value)
 
 
+def _scan(parent, op, columnwise, name):
+    """GxB_Matrix_scan / GxB_Vector_scan of ``parent`` into a new object of the monoid's type."""
+    from .matrix import Matrix
+    from .vector import Vector
+
+    mon = _scan_monoid(parent, _op.monoid.plus if op is None else op)
+    dtype = lookup_dtype(mon.type)
+    is_vector = parent.ndim == 1
+    desc = None if is_vector else descriptor_lookup(transpose_first=columnwise)
+    if dtype != parent.dtype:
+        # prefix_scan returns a dup, in the input's type, when nothing is folded: fewer than two
+        # positions along the scan, or no row with two entries.  Only here can that type show.
+        along = parent._size if is_vector else parent._nrows if columnwise else parent._ncols
+        longest = 0
+        if along >= 2:
+            if is_vector:
+                longest = parent.nvals
+            else:
+                width = _IndexOut("&k")
+                call("GxB_Matrix_compactify_width", [width, parent, desc])
+                longest = width.value.value
+        if longest < 2:
+            return parent.dup(name=name)
+    if is_vector:
+        out = Vector(dtype, parent._size, name=name)
+        call("GxB_Vector_scan", [out, mon, parent, desc])
+    else:
+        out = Matrix(dtype, parent._nrows, parent._ncols, name=name)
+        call("GxB_Matrix_scan", [out, mon, parent, desc])
+    return out
+
+
 class VectorSS:
     def __init__(self, parent):
         self._parent = parent
 
     def scan(self, op=None, *, name=None):
-        """Prefix scan with a monoid (reference core/ss/vector.py:1365-1375)."""
-        return prefix_scan(self._parent, _op.monoid.plus if op is None else op, name=name)
+        """GxB_Vector_scan (reference core/ss/vector.py:1365-1375): the inclusive prefix scan of the
+        entries in index order under a monoid (default plus), in the monoid's type."""
+        return _scan(self._parent, op, False, name)
 
     def sort(self, op=_op.binary.lt, *, values=True, permutation=True, **opts):
         """GxB_Vector_sort (reference core/ss/vector.py:1562-1617): ``(w, p)``, the values in
@@ -599,11 +636,9 @@ class MatrixSS:
         self._parent = parent
 
     def scan(self, op=None, order="rowwise", *, name=None):
-        """Prefix scan along rows (default) or columns (reference core/ss/matrix.py:3701-3715)."""
-        parent = self._parent
-        if _order(order) == "columnwise":
-            parent = parent.T
-        return prefix_scan(parent, _op.monoid.plus if op is None else op, name=name)
+        """GxB_Matrix_scan (reference core/ss/matrix.py:3701-3715): the inclusive prefix scan of
+        every row (column, if columnwise) under a monoid (default plus), in the monoid's type."""
+        return _scan(self._parent, op, _order(order) == "columnwise", name)
 
     def sort(self, op=_op.binary.lt, order="rowwise", *, values=True, permutation=True, **opts):
         """GxB_Matrix_sort (reference core/ss/matrix.py:3991-4055): ``(C, P)``, the values of

@@ -395,6 +395,23 @@ GrB_Info GxB_Vector_compactify(GrB_Vector w, const GrB_Vector u, int how, GrB_In
                                bool reverse, bool asindex, uint64_t seed,
                                const GrB_Descriptor desc);
 GrB_Info GxB_Matrix_compactify_width(GrB_Index *k, const GrB_Matrix A, const GrB_Descriptor desc);
+/* scan (reference core/ss/matrix.py:3701-3715, core/ss/vector.py:1365-1375): the inclusive prefix
+ * scan of every row of A (every column under GrB_DESC_T0; a vector is one row) under a builtin
+ * monoid.  C has A's structure and shape; C(i, j) folds, under op, the stored values of row i at
+ * columns <= j in ascending column order (of column j at rows <= i under T0).  A's values are
+ * cast to the monoid's type and the arithmetic is done in it, with the reductions' operators:
+ * integers wrap, float MIN / MAX ignore NaN.  ANY returns A's values.  The association order
+ * depends on the entry's position p (from 0) among its row's stored entries alone: write p + 1
+ * in binary; every set bit, from the highest down, stands for the next aligned block of 2^k
+ * entries, folded as a balanced pairwise tree (left half op right half); the blocks are combined
+ * left to right, largest first.  (Position 5: ((x0 op x1) op (x2 op x3)) op (x4 op x5).)  Row
+ * lengths, neighbouring rows, knobs and grid sizes do not change a bit of the result, and a
+ * vector's equals that of the 1 x n matrix with the same entries.  No mask, no accumulator: C is
+ * replaced, takes the result cast to its type, and may be A.  An iso A gives an iso C under an
+ * idempotent monoid (MIN, MAX, ANY, LOR, LAND, BOR, BAND).  A NULL C, op or A is
+ * GrB_NULL_POINTER, a C of another shape GrB_DIMENSION_MISMATCH; on any error C is untouched. */
+GrB_Info GxB_Matrix_scan(GrB_Matrix C, const GrB_Monoid op, const GrB_Matrix A, const GrB_Descriptor desc);
+GrB_Info GxB_Vector_scan(GrB_Vector w, const GrB_Monoid op, const GrB_Vector u, const GrB_Descriptor desc);
 /* eWiseUnion (reference core/matrix.py:2044-2161, core/vector.py:1141-1260): C<M> = accum(C, T),
  * T on the structure of A' union B' (after GrB_INP0 / GrB_INP1) with the type of add's result:
  * add(A'(i,j), B'(i,j)) where both are stored, add(A'(i,j), beta) where only A' is and
@@ -690,7 +707,11 @@ GrB_Info GxB_MatrixMarket_free(void *p);
  * "selectk_wave_max" / "selectk_block_max" (the same two bounds for the value and random modes
  * of selectk / compactify) and "stat_selectk_rows_all" / "_wave" / "_block" / "_long" (rows the
  * last such matrix call kept whole because they have at most k entries, and rows of two or more
- * entries each class ranked),
+ * entries each class ranked), "scan_wave_max" / "scan_block_max" / "scan_chunk" (the longest row
+ * of GxB_Matrix_scan's sub-wave and workgroup classes and the chunk of its long rows, a power of
+ * two from 64 up: they can only be lowered and read back as their defaults while unset) and
+ * "stat_scan_rows_wave" / "_block" / "_long" (rows of two or more entries each class took in the
+ * last scan),
  * "stat_union_both" / "stat_union_a_only" / "stat_union_b_only" (entries of T the last
  * eWiseUnion computed from both operands, from A' and beta, from alpha and B'),
  * "stat_concat_bitmap" / "stat_split_bitmap" (1 when the last concat / split moved bitmaps, 0
