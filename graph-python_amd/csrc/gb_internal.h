@@ -493,6 +493,20 @@ void gb_csr_col_to_bitmap(const gb_csr_view &v, size_t tsize, uint64_t **bits, v
 void gb_build(GB_Obj *C, const GrB_Index *I, const GrB_Index *J, const void *X, int xcode, bool x_iso,
               int64_t n, GrB_BinaryOp dup);
 void gb_extract_tuples(GB_Obj *A, GrB_Index *I, GrB_Index *J, void *X, int xcode, GrB_Index *nvals);
+// The device core of the build, shared by gb_build (host arrays) and gb_sparse_io.hip (device
+// arrays).  gb_coo_fold: keys (row << 32 | col, bounds-checked) and perm (the identity), n of each,
+// are sorted in place and duplicates folded in input order over X_dev (values in `code`; dup_opcode
+// < 0 keeps the last): unique keys, folded values and their count come back, caller-owned.
+// gb_build_install: such unique sorted tuples (owned from here on) become the storage of the empty
+// object C; Xc, the values they were folded from, supplies the iso value under gb_build's dup rule.
+void gb_coo_fold(uint64_t *keys, int64_t *perm, const void *X_dev, bool x_iso, int64_t n, int64_t nrows, int code,
+                 int dup_opcode, uint64_t **ukeys_out, void **uvals_out, int64_t *nu_out);
+bool gb_build_keeps_iso(GrB_BinaryOp dup);  // a one-scalar build stays iso under this dup (NULL: yes)
+void gb_build_install(GB_Obj *C, uint64_t *ukeys, void *uvals, int64_t nu, const void *Xc, bool x_iso,
+                      GrB_BinaryOp dup);
+// the entries of a bitmap vector in index order: dI (nvals indices) and, unless null, dX (nvals
+// values in the vector's type), both on the device
+void gb_vector_tuples(GB_Obj *A, uint64_t *dI, void *dX);
 
 // expand iso values to a full array of n elements
 void *gb_expand_iso(const void *one_value, size_t tsize, int64_t n);

@@ -448,25 +448,12 @@ __global__ void k_scatter_vec(const uint64_t *__restrict__ ukeys, const T *__res
     }
 }
 
-// Sort + dedupe COO tuples on the device.  Returns unique keys (row<<32|col)
-// and folded values (already in `code`), count in *nu.
-static void coo_sort_fold(const GrB_Index *I, const GrB_Index *J, const void *X_dev, bool x_iso,
-                          int64_t n, int64_t nrows, int64_t ncols, int code, int dup_opcode,
-                          uint64_t **ukeys_out, void **uvals_out, int64_t *nu_out) {
+// Sort + dedupe keyed COO tuples, all on the device.  keys (row<<32|col, bounds-checked) and perm
+// (the identity) are sorted in place; X_dev holds the values in `code`.  Returns unique keys and
+// folded values, count in *nu.
+void gb_coo_fold(uint64_t *keys, int64_t *perm, const void *X_dev, bool x_iso, int64_t n, int64_t nrows, int code,
+                 int dup_opcode, uint64_t **ukeys_out, void **uvals_out, int64_t *nu_out) {
     gb_scratch s;
-    uint64_t *dI = s.get<uint64_t>(n), *dJ = J ? s.get<uint64_t>(n) : nullptr;
-    gb_copy_h2d(dI, I, n * sizeof(uint64_t));
-    if (J) gb_copy_h2d(dJ, J, n * sizeof(uint64_t));
-    uint64_t *keys = s.get<uint64_t>(n);
-    int64_t *perm = s.get<int64_t>(n);
-    int *bad = s.get<int>(1);
-    gb_memset(bad, 0, sizeof(int));
-    hipLaunchKernelGGL(k_check_and_key, dim3(gb_grid(n, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0, gb_stream(), dI,
-                       dJ, n, (uint64_t)nrows, (uint64_t)ncols, keys, perm, bad);
-    GB_LAUNCH_CHECK();
-    int hbad = 0;
-    gb_copy_d2h(&hbad, bad, sizeof(int));
-    GB_REQUIRE(!hbad, GrB_INDEX_OUT_OF_BOUNDS, "index out of bounds in build");
     int rbits = 1;
     while (rbits < 31 && (1LL << rbits) < nrows) rbits++;
     gb_sort_pairs_u64(keys, perm, n, 32 + rbits);
@@ -489,34 +476,44 @@ static void coo_sort_fold(const GrB_Index *I, const GrB_Index *J, const void *X_
     *nu_out = nu;
 }
 
-void gb_build(GB_Obj *C, const GrB_Index *I, const GrB_Index *J, const void *X, int xcode,
-                         bool x_iso, int64_t n, GrB_BinaryOp dup) {
-    GB_REQUIRE(C->kind == GB_KIND_MATRIX || C->ncols == 1, GrB_INVALID_OBJECT, "bad build target");
-    GB_REQUIRE(gb_nvals(C) == 0, GrB_OUTPUT_NOT_EMPTY, "output is not empty");
-    if (n == 0) return;
-    GB_REQUIRE(I && (J || C->kind != GB_KIND_MATRIX) && X, GrB_NULL_POINTER, "NULL build array");
+// host staging of the index arrays, then the device core
+static void coo_sort_fold(const GrB_Index *I, const GrB_Index *J, const void *X_dev, bool x_iso,
+                          int64_t n, int64_t nrows, int64_t ncols, int code, int dup_opcode,
+                          uint64_t **ukeys_out, void **uvals_out, int64_t *nu_out) {
+    gb_scratch s;
+    uint64_t *dI = s.get<uint64_t>(n), *dJ = J ? s.get<uint64_t>(n) : nullptr;
+    gb_copy_h2d(dI, I, n * sizeof(uint64_t));
+    if (J) gb_copy_h2d(dJ, J, n * sizeof(uint64_t));
+    uint64_t *keys = s.get<uint64_t>(n);
+    int64_t *perm = s.get<int64_t>(n);
+    int *bad = s.get<int>(1);
+    gb_memset(bad, 0, sizeof(int));
+    hipLaunchKernelGGL(k_check_and_key, dim3(gb_grid(n, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0, gb_stream(), dI,
+                       dJ, n, (uint64_t)nrows, (uint64_t)ncols, keys, perm, bad);
+    GB_LAUNCH_CHECK();
+    int hbad = 0;
+    gb_copy_d2h(&hbad, bad, sizeof(int));
+    GB_REQUIRE(!hbad, GrB_INDEX_OUT_OF_BOUNDS, "index out of bounds in build");
+    gb_coo_fold(keys, perm, X_dev, x_iso, n, nrows, code, dup_opcode, ukeys_out, uvals_out, nu_out);
+}
+
+// a build from one scalar stays iso under these dup operators: folding equal values changes nothing
+bool gb_build_keeps_iso(GrB_BinaryOp dup) {
+    return dup == nullptr || dup->opcode == GBAMD_OP_FIRST || dup->opcode == GBAMD_OP_SECOND ||
+           dup->opcode == GBAMD_OP_ANY || dup->opcode == GBAMD_OP_MIN || dup->opcode == GBAMD_OP_MAX ||
+           dup->opcode == GBAMD_OP_LOR || dup->opcode == GBAMD_OP_LAND;
+}
+
+// The unique sorted tuples of a build (ukeys, uvals in C's type: owned from here on; Xc: the
+// device values the tuples came from, read for the iso value) become C's storage.
+void gb_build_install(GB_Obj *C, uint64_t *ukeys, void *uvals, int64_t nu, const void *Xc, bool x_iso,
+                      GrB_BinaryOp dup) {
     int code = C->type->code;
     size_t ts = C->type->size;
     gb_scratch s;
-    int64_t nx = x_iso ? 1 : n;
-    void *Xraw = s.get<char>(nx * gb_type_size(xcode));
-    gb_copy_h2d(Xraw, X, nx * gb_type_size(xcode));
-    void *Xc = Xraw;
-    if (xcode != code) {
-        Xc = s.get<char>(nx * ts);
-        gb_cast_array(Xc, code, Xraw, xcode, nx);
-    }
-    int dupop = dup ? dup->opcode : -1;
-    uint64_t *ukeys;
-    void *uvals;
-    int64_t nu;
     bool is_vec = C->kind != GB_KIND_MATRIX;
-    coo_sort_fold(I, is_vec ? nullptr : J, Xc, x_iso, n, C->nrows, is_vec ? 1 : C->ncols, code, dupop,
-                  &ukeys, &uvals, &nu);
     if (x_iso) {  // every folded value equals the scalar unless a dup op changed it
-        if (dup == nullptr || dup->opcode == GBAMD_OP_FIRST || dup->opcode == GBAMD_OP_SECOND ||
-            dup->opcode == GBAMD_OP_ANY || dup->opcode == GBAMD_OP_MIN || dup->opcode == GBAMD_OP_MAX ||
-            dup->opcode == GBAMD_OP_LOR || dup->opcode == GBAMD_OP_LAND) {
+        if (gb_build_keeps_iso(dup)) {
             gb_free(uvals);
             uvals = gb_malloc(ts);
             gb_copy_d2d(uvals, Xc, ts);
@@ -556,6 +553,33 @@ void gb_build(GB_Obj *C, const GrB_Index *I, const GrB_Index *J, const void *X, 
         C->nvals = nu;
         C->nvals_valid = true;
     }
+}
+
+void gb_build(GB_Obj *C, const GrB_Index *I, const GrB_Index *J, const void *X, int xcode,
+                         bool x_iso, int64_t n, GrB_BinaryOp dup) {
+    GB_REQUIRE(C->kind == GB_KIND_MATRIX || C->ncols == 1, GrB_INVALID_OBJECT, "bad build target");
+    GB_REQUIRE(gb_nvals(C) == 0, GrB_OUTPUT_NOT_EMPTY, "output is not empty");
+    if (n == 0) return;
+    GB_REQUIRE(I && (J || C->kind != GB_KIND_MATRIX) && X, GrB_NULL_POINTER, "NULL build array");
+    int code = C->type->code;
+    size_t ts = C->type->size;
+    gb_scratch s;
+    int64_t nx = x_iso ? 1 : n;
+    void *Xraw = s.get<char>(nx * gb_type_size(xcode));
+    gb_copy_h2d(Xraw, X, nx * gb_type_size(xcode));
+    void *Xc = Xraw;
+    if (xcode != code) {
+        Xc = s.get<char>(nx * ts);
+        gb_cast_array(Xc, code, Xraw, xcode, nx);
+    }
+    int dupop = dup ? dup->opcode : -1;
+    uint64_t *ukeys;
+    void *uvals;
+    int64_t nu;
+    bool is_vec = C->kind != GB_KIND_MATRIX;
+    coo_sort_fold(I, is_vec ? nullptr : J, Xc, x_iso, n, C->nrows, is_vec ? 1 : C->ncols, code, dupop,
+                  &ukeys, &uvals, &nu);
+    gb_build_install(C, ukeys, uvals, nu, Xc, x_iso, dup);
 }
 
 // ================================================================== extract
@@ -600,6 +624,24 @@ static void values_to_host(void *host, int code, const void *dvals, int src_code
     }
 }
 
+// the entries of a bitmap vector in index order, on the device: dI (nvals indices) and, when not
+// null, dX (nvals values in the vector's type; an iso vector's value is written nvals times)
+void gb_vector_tuples(GB_Obj *A, uint64_t *dI, void *dX) {
+    gb_scratch s;
+    int64_t n = A->nrows, nw = gb_words(n);
+    int64_t *pop = s.get<int64_t>(nw), *woff = s.get<int64_t>(nw + 1);
+    hipLaunchKernelGGL(k_word_pop2, dim3(gb_grid(nw, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0, gb_stream(), A->bits,
+                       nw, pop);
+    GB_LAUNCH_CHECK();
+    gb_exclusive_scan_i64(pop, woff, nw);
+    gb_with_type(A->type->code, [&](auto z) {
+        using T = decltype(z);
+        hipLaunchKernelGGL(k_bitmap_compact<T>, dim3(gb_grid(n, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0,
+                           gb_stream(), A->bits, (const T *)A->dense, A->iso, n, woff, dI, (T *)dX);
+    });
+    GB_LAUNCH_CHECK();
+}
+
 void gb_extract_tuples(GB_Obj *A, GrB_Index *I, GrB_Index *J, void *X, int xcode, GrB_Index *nvals) {
     GB_REQUIRE(nvals, GrB_NULL_POINTER, "nvals is NULL");
     int64_t nz = gb_nvals(A);
@@ -623,20 +665,9 @@ void gb_extract_tuples(GB_Obj *A, GrB_Index *I, GrB_Index *J, void *X, int xcode
         if (X) values_to_host(X, xcode, A->vals, A->type->code, A->iso, nz);
         return;
     }
-    int64_t n = A->nrows, nw = gb_words(n);
-    int64_t *pop = s.get<int64_t>(nw), *woff = s.get<int64_t>(nw + 1);
-    hipLaunchKernelGGL(k_word_pop2, dim3(gb_grid(nw, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0, gb_stream(), A->bits,
-                       nw, pop);
-    GB_LAUNCH_CHECK();
-    gb_exclusive_scan_i64(pop, woff, nw);
     uint64_t *dI = s.get<uint64_t>(nz);
     void *dX = (X && !A->iso) ? s.get<char>(nz * A->type->size) : nullptr;
-    gb_with_type(A->type->code, [&](auto z) {
-        using T = decltype(z);
-        hipLaunchKernelGGL(k_bitmap_compact<T>, dim3(gb_grid(n, GB_BLOCK, OBJ_GRID_CAP)), dim3(GB_BLOCK), 0,
-                           gb_stream(), A->bits, (const T *)A->dense, A->iso, n, woff, dI, (T *)dX);
-    });
-    GB_LAUNCH_CHECK();
+    gb_vector_tuples(A, dI, dX);
     if (I) gb_copy_d2h(I, dI, nz * sizeof(uint64_t));
     if (J) memset(J, 0, nz * sizeof(GrB_Index));
     if (X) {

@@ -80,6 +80,10 @@ _SIGS = {
     "GxB_Vector_import_dense": [P, P, I, P, P, P, ctypes.c_bool],
     "GxB_Matrix_export_dense": [P, P, P, P, ctypes.c_bool, ctypes.c_bool],
     "GxB_Vector_export_dense": [P, P, P, P, ctypes.c_bool],
+    "GxB_Matrix_import_sparse": [P, P, I, I, P, P, P, P, P, I, I, I, E, P, ctypes.c_bool],
+    "GxB_Vector_import_sparse": [P, P, I, P, P, P, P, I, I, P, ctypes.c_bool],
+    "GxB_Matrix_export_sparse": [P, P, P, P, P, P, P, P, E, P, ctypes.c_bool],
+    "GxB_Vector_export_sparse": [P, P, P, P, P, P, P, ctypes.c_bool],
     "GrB_Vector_assign": [P, P, P, P, P, I, P], "GrB_Matrix_assign": [P, P, P, P, P, I, P, I, P],
     "GrB_Matrix_reduce_Monoid_Scalar": [P] * 5, "GrB_Vector_reduce_Monoid_Scalar": [P] * 5,
     "GrB_transpose": [P] * 5,

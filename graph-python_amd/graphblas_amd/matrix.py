@@ -116,6 +116,10 @@ class Matrix(BaseType):
     @classmethod
     def from_coo(cls, rows, columns, values=1.0, dtype=None, *, nrows=None, ncols=None, dup_op=None,
                  name=None):
+        from . import sparse
+
+        if sparse.any_device(rows, columns, values):  # device arrays never leave the device
+            return sparse.matrix_from_coo(cls, rows, columns, values, dtype, nrows, ncols, dup_op, name)
         rows = _index_array(rows, "row indices")
         columns = _index_array(columns, "column indices")
         if nrows is None:
@@ -143,6 +147,13 @@ class Matrix(BaseType):
         return C
 
     def build(self, rows, columns, values, *, dup_op=None, clear=False, nrows=None, ncols=None):
+        from . import sparse
+
+        if sparse.any_device(rows, columns, values):
+            nr, nc = self._nrows if nrows is None else int(nrows), self._ncols if ncols is None else int(ncols)
+            sparse.matrix_from_coo(Matrix, rows, columns, values, self.dtype, nr, nc, dup_op, None, "build",
+                                   into=self, clear=clear)
+            return
         rows = _index_array(rows, "row indices")
         columns = _index_array(columns, "column indices")
         values = np.ascontiguousarray(np.broadcast_to(np.asarray(values, self.dtype.np_type), rows.shape))
@@ -163,9 +174,15 @@ class Matrix(BaseType):
             raise ValueError("Duplicate indices found, must provide `dup_op` BinaryOp")
 
     @classmethod
-    def from_csr(cls, indptr, col_indices, values=1.0, dtype=None, *, ncols=None, name=None):
+    def from_csr(cls, indptr, col_indices, values=1.0, dtype=None, *, nrows=None, ncols=None, name=None):
+        from . import sparse
+
+        if sparse.any_device(indptr, col_indices, values):
+            return sparse.matrix_from_csx(cls, indptr, col_indices, values, dtype, nrows, ncols, name, by_col=False)
         indptr = np.ascontiguousarray(indptr, np.uint64)
         col_indices = np.ascontiguousarray(col_indices, np.uint64)
+        if nrows is not None and int(nrows) != indptr.size - 1:  # reference core/matrix.py:1073-1077
+            raise ValueError(f"nrows must be None or equal to len(indptr) - 1; expected {indptr.size - 1}, got {nrows}")
         nrows = indptr.size - 1
         if ncols is None:
             ncols = int(col_indices.max()) + 1 if col_indices.size else 0
@@ -180,6 +197,34 @@ class Matrix(BaseType):
         call(f"GrB_Matrix_import_{dt.name}",
              [_Pointer(C), dt, nrows, ncols, _CArray(indptr, "indptr"), _CArray(col_indices, "col"),
               _CArray(vals, "values"), indptr.size, col_indices.size, vals.size, lib.GrB_CSR_FORMAT])
+        return C
+
+    @classmethod
+    def from_csc(cls, indptr, row_indices, values=1.0, dtype=None, *, nrows=None, ncols=None, name=None):
+        """The Matrix of a CSC triple (reference core/matrix.py:1180-1222): host arrays through
+        GrB_Matrix_import with GrB_CSC_FORMAT, device arrays through GxB_Matrix_import_sparse."""
+        from . import sparse
+
+        if sparse.any_device(indptr, row_indices, values):
+            return sparse.matrix_from_csx(cls, indptr, row_indices, values, dtype, nrows, ncols, name, by_col=True)
+        indptr = np.ascontiguousarray(indptr, np.uint64)
+        row_indices = np.ascontiguousarray(row_indices, np.uint64)
+        if ncols is not None and int(ncols) != indptr.size - 1:  # reference core/matrix.py:1081-1085
+            raise ValueError(f"ncols must be None or equal to len(indptr) - 1; expected {indptr.size - 1}, got {ncols}")
+        ncols = indptr.size - 1
+        if nrows is None:
+            nrows = int(row_indices.max()) + 1 if row_indices.size else 0
+        vals = np.asarray(values)
+        dt = _values_dtype(vals, dtype)
+        vals = np.ascontiguousarray(np.broadcast_to(np.asarray(vals, dt.np_type), row_indices.shape))
+        C = cls.__new__(cls)
+        C.dtype = dt
+        C.name = _autoname("M") if name is None else name
+        C._h = ctypes.c_void_p()
+        C._nrows, C._ncols = int(nrows), int(ncols)
+        call(f"GrB_Matrix_import_{dt.name}",
+             [_Pointer(C), dt, nrows, ncols, _CArray(indptr, "indptr"), _CArray(row_indices, "row"),
+              _CArray(vals, "values"), indptr.size, row_indices.size, vals.size, lib.GrB_CSC_FORMAT])
         return C
 
     @classmethod
@@ -207,20 +252,43 @@ class Matrix(BaseType):
 
         return to_dense(self, fill_value, dtype, out, bitmap, upcast=True)
 
-    def to_csr(self, dtype=None):
+    def to_csr(self, dtype=None, *, sort=True, device=False, index_dtype="int64"):
+        """(indptr, col_indices, values).  ``device=True``: torch CUDA tensors written on the device
+        (GxB_Matrix_export_sparse), indices int64 or, with ``index_dtype="int32"``, int32; the library
+        stream is waited on, so the tensors are complete on any stream."""
+        if device:
+            from .sparse import matrix_export
+
+            return matrix_export(self, "csr", dtype, index_dtype, (True, True, True))
+        return self._to_csx(dtype, lib.GrB_CSR_FORMAT, self._nrows + 1)
+
+    def to_csc(self, dtype=None, *, sort=True, device=False, index_dtype="int64"):
+        """(indptr, row_indices, values) (reference core/matrix.py:1704-1727); ``device`` as in to_csr."""
+        if device:
+            from .sparse import matrix_export
+
+            return matrix_export(self, "csc", dtype, index_dtype, (True, True, True))
+        return self._to_csx(dtype, lib.GrB_CSC_FORMAT, self._ncols + 1)
+
+    def _to_csx(self, dtype, fmt, np_len):
         dt = self.dtype if dtype is None else lookup_dtype(dtype)
         n = self.nvals
-        ap = np.empty(self._nrows + 1, np.uint64)
+        ap = np.empty(np_len, np.uint64)
         ai = np.empty(n, np.uint64)
         ax = np.empty(n, dt.np_type)
         lens = [ctypes.c_uint64(ap.size), ctypes.c_uint64(ai.size), ctypes.c_uint64(ax.size)]
         rc = getattr(lib, f"GrB_Matrix_export_{dt.name}")(
             ctypes.c_void_p(ap.ctypes.data), ctypes.c_void_p(ai.ctypes.data),
-            ctypes.c_void_p(ax.ctypes.data), *[ctypes.byref(x) for x in lens], lib.GrB_CSR_FORMAT, self._h)
+            ctypes.c_void_p(ax.ctypes.data), *[ctypes.byref(x) for x in lens], fmt, self._h)
         check_status_carg(rc, "Matrix", self._h)
         return ap.astype(np.int64), ai.astype(np.int64), ax
 
-    def to_coo(self, dtype=None, *, rows=True, columns=True, values=True, sort=True):
+    def to_coo(self, dtype=None, *, rows=True, columns=True, values=True, sort=True, device=False,
+               index_dtype="int64"):
+        if device:  # torch CUDA tensors written on the device; an array that is not wanted is not exported
+            from .sparse import matrix_export
+
+            return matrix_export(self, "coo", dtype, index_dtype, (rows, columns, values))
         dt = self.dtype if dtype is None else lookup_dtype(dtype)
         n = self.nvals
         r = np.empty(n, np.uint64)
@@ -755,10 +823,19 @@ class TransposedMatrix:
     def kronecker(self, other, op=None):
         return _kronecker(self, other, op)
 
-    def to_coo(self, *args, **kw):
+    def to_coo(self, *args, device=False, index_dtype="int64", **kw):
+        if device:  # the transpose is built on the device (GrB_transpose) and exported row-major
+            return self.new().to_coo(*args, device=True, index_dtype=index_dtype, **kw)
         r, c, v = self._matrix.to_coo(*args, **kw)
         o = np.lexsort((r, c))
         return c[o], r[o], v[o]
+
+    def to_csr(self, dtype=None, *, sort=True, device=False, index_dtype="int64"):
+        """The CSR of the transpose is the matrix' CSC: nothing is transposed."""
+        return self._matrix.to_csc(dtype, sort=sort, device=device, index_dtype=index_dtype)
+
+    def to_csc(self, dtype=None, *, sort=True, device=False, index_dtype="int64"):
+        return self._matrix.to_csr(dtype, sort=sort, device=device, index_dtype=index_dtype)
 
     def to_dense(self, fill_value=None, dtype=None, *, out=None, bitmap=None):
         """As Matrix.to_dense: the column-major export of the matrix, nothing is transposed."""

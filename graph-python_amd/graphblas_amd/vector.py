@@ -70,6 +70,10 @@ class Vector(BaseType):
     # ---------------------------------------------------------------- construction
     @classmethod
     def from_coo(cls, indices, values=1.0, dtype=None, *, size=None, dup_op=None, name=None):
+        from . import sparse
+
+        if sparse.any_device(indices, values):  # device arrays never leave the device
+            return sparse.vector_from_coo(cls, indices, values, dtype, size, dup_op, name)
         indices = _index_array(indices, "indices")
         if size is None:
             size = int(indices.max()) + 1 if indices.size else 0
@@ -90,6 +94,12 @@ class Vector(BaseType):
         return v
 
     def build(self, indices, values, *, dup_op=None, clear=False, size=None):
+        from . import sparse
+
+        if sparse.any_device(indices, values):
+            sparse.vector_from_coo(Vector, indices, values, self.dtype, self._size if size is None else int(size),
+                                   dup_op, None, "build", into=self, clear=clear)
+            return
         indices = _index_array(indices, "indices")
         values = np.ascontiguousarray(np.broadcast_to(np.asarray(values, self.dtype.np_type), indices.shape))
         n = values.shape[0]
@@ -107,7 +117,11 @@ class Vector(BaseType):
         if dup_op is None and self.nvals < n:
             raise ValueError("Duplicate indices found, must provide `dup_op` BinaryOp")
 
-    def to_coo(self, dtype=None, *, indices=True, values=True, sort=True):
+    def to_coo(self, dtype=None, *, indices=True, values=True, sort=True, device=False, index_dtype="int64"):
+        if device:  # torch CUDA tensors written on the device (GxB_Vector_export_sparse)
+            from .sparse import vector_export
+
+            return vector_export(self, dtype, index_dtype, (indices, values))
         dt = self.dtype if dtype is None else lookup_dtype(dtype)
         n = self.nvals
         idx = np.empty(n, np.uint64)

@@ -490,6 +490,41 @@ GrB_Info GxB_Matrix_export_dense(void *X, int8_t *Ab, const GrB_Matrix A, const 
 GrB_Info GxB_Vector_export_dense(void *X, int8_t *Ab, const GrB_Vector v, const GrB_Scalar fill,
                                  bool on_device);
 
+/* sparse import / export from host or device arrays (reference core/matrix.py:885-960, :1057-1133,
+ * :543-611, :1658-1702; this library's own names, for the reason above).  on_device true: the
+ * pointers are device addresses, read or written on the library stream (the caller has finished
+ * producing the arrays and waits on the object or the stream afterwards); false: host pointers,
+ * staged by one copy each.  index_type is GrB_INT32, GrB_INT64 or GrB_UINT64 (Ap has Ai's type;
+ * anything else: GrB_DOMAIN_MISMATCH); a negative index is out of bounds, it does not wrap.
+ * value_type is any builtin type; values are cast to `type` (export: to value_type) on the device
+ * as every typecast of the library is.  Ax_len == 1 with more than one index: one value for every
+ * entry, and the result is iso where GrB_Matrix_build of a scalar makes it iso.
+ * import, GrB_COO_FORMAT: Ap holds rows and Ai columns, Ap_len == Ai_len tuples; duplicates are
+ * folded in input order with dup (NULL: the last one is kept).  GrB_CSR_FORMAT / GrB_CSC_FORMAT: Ap
+ * is the pointer of nrows + 1 / ncols + 1 entries; dup is not used, a jumbled row is sorted and of
+ * duplicates in a row the last is kept.  Checked before any array is addressed through it, and
+ * GrB_INVALID_VALUE: Ap[0] == 0, Ap never decreases, Ap[last] <= Ai_len, Ax_len is 1 or >= Ap[last]
+ * (COO: Ap_len == Ai_len, Ax_len is 1 or >= Ai_len); an index outside the dimensions is
+ * GrB_INDEX_OUT_OF_BOUNDS.  A refused import leaves *A unset.  GxB_Global_get_int
+ * ("stat_sparse_import_path") tells which way the last import went: 0 the input was strictly
+ * increasing and was installed as it is, 1 sorted and folded, 2 compressed input found jumbled.
+ * export: on entry the lengths are the arrays' capacities, on return the lengths used (too small:
+ * GrB_INSUFFICIENT_SPACE, nothing written).  A NULL array is not written (Ax == NULL: the structure
+ * only).  COO is sorted by row, then column.  GrB_INT32 indices need every dimension and nvals
+ * below 2^31: GrB_INVALID_VALUE otherwise. */
+GrB_Info GxB_Matrix_import_sparse(GrB_Matrix *A, GrB_Type type, GrB_Index nrows, GrB_Index ncols,
+                                  const void *Ap, const void *Ai, const void *Ax, GrB_Type index_type,
+                                  GrB_Type value_type, GrB_Index Ap_len, GrB_Index Ai_len, GrB_Index Ax_len,
+                                  GrB_Format format, const GrB_BinaryOp dup, bool on_device);
+GrB_Info GxB_Vector_import_sparse(GrB_Vector *v, GrB_Type type, GrB_Index n, const void *Ai, const void *Ax,
+                                  GrB_Type index_type, GrB_Type value_type, GrB_Index Ai_len, GrB_Index Ax_len,
+                                  const GrB_BinaryOp dup, bool on_device);
+GrB_Info GxB_Matrix_export_sparse(void *Ap, void *Ai, void *Ax, GrB_Type index_type, GrB_Type value_type,
+                                  GrB_Index *Ap_len, GrB_Index *Ai_len, GrB_Index *Ax_len, GrB_Format format,
+                                  const GrB_Matrix A, bool on_device);
+GrB_Info GxB_Vector_export_sparse(void *Ai, void *Ax, GrB_Type index_type, GrB_Type value_type,
+                                  GrB_Index *Ai_len, GrB_Index *Ax_len, const GrB_Vector v, bool on_device);
+
 /* ---------------------------------------------------------------- the hot path */
 /* C<Mask> = C accum (A' (+).(x) B')      replaces SuiteSparse GrB_mxm */
 GrB_Info GrB_mxm(GrB_Matrix C, const GrB_Matrix Mask, const GrB_BinaryOp accum,
