@@ -262,6 +262,10 @@ static struct {
 } g_spec;
 
 bool gb_deferred_stat(const char *key, int64_t *value) {
+    if (!strcmp(key, "stat_deferred_live")) {  // read without resolving: what the next call will meet
+        *value = (int64_t)g_deferred.load(std::memory_order_acquire);
+        return true;
+    }
     const bool adopted = !strcmp(key, "stat_bfs_spec_adopted");
     if (!adopted && strcmp(key, "stat_bfs_spec_rollbacks")) return false;
     *value = (adopted ? g_stat_adopted : g_stat_rollbacks).load(std::memory_order_relaxed);
@@ -539,6 +543,11 @@ void gb_do_spmv(GB_Obj *w, GB_Obj *mask, GrB_BinaryOp accum, GrB_Semiring sr, GB
                 take_pending_assign(asg, w, mask, A, u, d, gb_spmv_result_iso(sr, A->iso, u->iso, vxm));
         if (!fused) gb_deferred_resolve(0, nullptr);
     }
+    // a pending root that this call cannot consume (below: only the fused notebook level can) is
+    // materialised before the views are built: a value mask is resolved into bits of its own
+    // there, and one resolved from a pending root's storage would be the empty vector's
+    const bool may_take_root = fused && u == w && !accum && d.replace && d.comp && d.structure;
+    if (live(GB_DEFER_ROOT) && !may_take_root) root_flush();
     const int64_t hp_t0 = g_hprof_on ? gb_hprof_now() : 0;
     spmv_views V;
     spmv_build_views(V, mask, sr, A, u, d, vxm, a_rows, fused ? &asg : nullptr);
@@ -547,8 +556,8 @@ void gb_do_spmv(GB_Obj *w, GB_Obj *mask, GrB_BinaryOp accum, GrB_Semiring sr, GB
     // q (+).(x) A with the stamp v<q> = x fused, iso result, push orientation at hand -- whose kernel
     // pushes from it; materialised before any other SpMV
     if (live(GB_DEFER_ROOT)) {
-        const bool shape = fused && u == w && !accum && d.replace && d.comp && d.structure && V.iso_result &&
-                           V.push && V.push->nrows == u->nrows && V.push->hubs && gb_knob("spmv_direction") != 1;
+        const bool shape = may_take_root && V.iso_result && V.push && V.push->nrows == u->nrows && V.push->hubs &&
+                           gb_knob("spmv_direction") != 1;
         if (shape) asg.root = root_take(u);
         if (asg.root >= 0) {
             // u's storage does not hold the root: its iso value (true) and count come from the host

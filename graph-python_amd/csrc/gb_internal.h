@@ -213,7 +213,8 @@ bool gb_stamp_try_defer(GB_Obj *w, GB_Obj *mask, const char *xc, const gb_desc &
 // speculation predicted and already carried out (absorbed), or matching it failed
 bool gb_deferred_absorb_assign(GrB_Vector w, GrB_Vector mask, GrB_BinaryOp accum, const void *x, int xcode,
                                const GrB_Index *I, GrB_Index ni, GrB_Descriptor desc, GrB_Info *info);
-bool gb_deferred_stat(const char *key, int64_t *value);  // "stat_bfs_spec_adopted" / "stat_bfs_spec_rollbacks"
+// "stat_bfs_spec_adopted" / "stat_bfs_spec_rollbacks" / "stat_deferred_live"
+bool gb_deferred_stat(const char *key, int64_t *value);
 // GrB_mxv / GrB_vxm (and the row reduction of gb_ops.hip): adopts, fuses or resolves what is live
 void gb_do_spmv(GB_Obj *w, GB_Obj *mask, GrB_BinaryOp accum, GrB_Semiring sr, GB_Obj *A, GB_Obj *u, const gb_desc &d,
                 bool vxm);

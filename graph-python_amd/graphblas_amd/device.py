@@ -40,6 +40,24 @@ def matrix_view(handle):
     return v
 
 
+def matrix_from_csr(dtype, nrows, ncols, rowptr, colidx, values, nvals, iso=False, *, name=None):
+    """A new Matrix from CSR arrays in device memory (GxB_Matrix_import_device; copied on the library
+    stream): device addresses of rowptr int64[nrows + 1], colidx int32[nvals] sorted and unique per
+    row, values [nvals] of `dtype`, or [1] when iso."""
+    from .base import _autoname, _Pointer, call
+    from .dtypes import lookup_dtype
+    from .matrix import Matrix
+
+    A = Matrix.__new__(Matrix)
+    A.dtype = lookup_dtype(dtype)
+    A.name = _autoname("M") if name is None else name
+    A._h = ctypes.c_void_p()
+    A._nrows, A._ncols = int(nrows), int(ncols)
+    call("GxB_Matrix_import_device", [_Pointer(A), A.dtype, A._nrows, A._ncols, ctypes.c_void_p(rowptr),
+                                      ctypes.c_void_p(colidx), ctypes.c_void_p(values), int(nvals), bool(iso)])
+    return A
+
+
 def colwords_view(handle):
     """(device address, count) of a <=64-row matrix's column words (GxB_Matrix_colwords_view);
     rewrite them in place on the library stream, then GxB_Matrix_colwords_touch."""

@@ -752,8 +752,11 @@ GrB_Info GxB_MatrixMarket_free(void *p);
  * "stat_concat_bitmap" / "stat_split_bitmap" (1 when the last concat / split moved bitmaps, 0
  * when it built CSR), "stat_concat_iso" (1 when the last concat's result was iso),
  * "stat_reshape_div64" (1 when the last reshape divided in 64 bits: 2^32 or more positions), the read-only counters "stat_bfs_spec_adopted" / "stat_bfs_spec_rollbacks" (BFS level
- * speculation) and "stat_nvals_copy" (vector counts read by a device copy
- * instead of the producing kernel's host mailbox). */
+ * speculation), "stat_deferred_live" (what the level loop has deferred right now, read
+ * without carrying it out: 1 a speculated level, 2 a pending root, 4 a deferred stamp, or their sum;
+ * a diagnostic for the test suite: its meaning follows the library's internals, do not rely on it)
+ * and "stat_nvals_copy" (vector counts read by a device copy instead of the producing kernel's host
+ * mailbox). */
 GrB_Info GxB_Global_set_int(const char *key, int64_t value);
 GrB_Info GxB_Global_get_int(const char *key, int64_t *value);
 
